@@ -19,12 +19,20 @@ groups and N C2 row groups per width; rank r decodes the row groups
 pqgpu.shard assigns it (RG i -> rank floor(i N / R)).  No collective touches
 the data path: only the timing barrier and the MAX of the elapsed time.
 
+A plain run (`--gpus 1 --steps N --warmup W`) does what the headline figure
+needs and nothing more: it generates and uploads the C2 files, warms up, times
+the N steps, writes the last timed step's outputs if `--dump-outputs DIR` is
+given, and prints one result line.  `--full` adds everything else described
+here (verification, the instrumented steps behind the rooflines, K8, the CPU
+baselines and the sub-results) and prints the full line, then the compact one.
+
 Metric: decoded GB/s of uncompressed output (SURVEY §8d B_out: values, 1 B per
 level per slot, string chars + 4 B offsets), whole job = sum over ranks / max
-time over ranks.  Outputs are verified bit-exact against the generator's
-arrays after timing.  The CPU baseline is the oracle (the C++ restatement of
-parquet-go's decode) timed on a bounded sample: one thread (parquet-go's
-one-goroutine FileReader) and a pool of host threads over independent chunks.
+time over ranks.  With --full, outputs are verified bit-exact against the
+generator's arrays after timing.  The CPU baseline is the oracle (the C++
+restatement of parquet-go's decode) timed on a bounded sample: one thread
+(parquet-go's one-goroutine FileReader) and a pool of host threads over
+independent chunks.
 """
 import argparse
 import ctypes as C
@@ -81,7 +89,9 @@ class Workload:
         self.devs = []
 
 
-def gen_workload(key, args, rank, world):
+def gen_workload(key, args, rank, world, expected=True):
+    """The files of one config for this rank.  expected=False drops C2's expected
+    arrays (only verify() and k8_c2 read them)."""
     import pqgpu
     from gen import pqwrite as W
     from pqgpu import shard
@@ -92,9 +102,10 @@ def gen_workload(key, args, rank, world):
         rgs = list(shard.row_groups_for_rank(world, rank, world))  # N row groups per width
         bits_list = [int(b) for b in args.bits.split(",")]
         for rg in rgs:
+            # the widths' files are written side by side on host threads
             for bits, data, exp in W.config_c2_family(rows=args.rows, bits_list=bits_list, seed=2 + rg,
-                                                      run_heavy=rh):
-                files.append((pqgpu.ParquetFile(data), [(0, 0)], ("c2", exp)))
+                                                      run_heavy=rh, workers=min(len(bits_list), host_cores()[0])):
+                files.append((pqgpu.ParquetFile(data), [(0, 0)], ("c2", exp if expected else None)))
         desc = ("C2%s: optional INT32, %d rows x %d dictionary widths (b=%s), ~10%% nulls, RLE_DICTIONARY (%s), V1, "
                 "UNCOMPRESSED, 20000 rows/page" % (" run-heavy" if rh else "", args.rows, len(bits_list), args.bits,
                                                   "index runs of geometric length, mean 16" if rh
@@ -167,6 +178,25 @@ def _level_sections(pf, meta, pg, desc):
         if present:
             pos += 4 + int.from_bytes(body[pos:pos + 4], "little")
     return pos, pg.uncompressed_size - pos
+
+
+def io_bytes(wl, res):
+    """B_in/B_out of the step from the footers and the chunk
+    results alone: what the headline value needs."""
+    b_in = b_out = 0
+    ji = 0
+    for pf, specs, _ in wl.files:
+        for (rg, col) in specs:
+            r = res[ji]
+            desc = pf.columns[col].desc
+            b_in += pf.chunk_meta(rg, col).total_compressed_size
+            slots_out = r.num_slots * ((desc.max_def > 0) + (desc.max_rep > 0))
+            if r.value_width:
+                b_out += r.num_values * r.value_width + slots_out
+            else:
+                b_out += r.values_bytes + (r.num_values + 1) * 4 + slots_out
+            ji += 1
+    return b_in, b_out
 
 
 def account(wl, pages_of, res):
@@ -246,6 +276,59 @@ def verify(wl, dec, res):
                 if e.get("rep_levels") is not None:
                     ok &= np.array_equal(dec.d2h(r.rep_levels, r.num_slots), e["rep_levels"])
     return bool(ok)
+
+
+# ---------------------------------------------------------------- output dump
+DUMP_BUDGET = 60 << 20  # bytes of .npy data per dump (the files stay under 64 MB in all)
+DUMP_BLOCKS = 4096      # block sums per array, at most
+VALUE_VIEW = {1: np.int32, 2: np.uint32, 3: np.uint32, 4: np.float32, 5: np.float64}  # by physical type
+
+
+def dump_outputs(wl, dec, res, out_dir, prefix=""):
+    """The device arrays of `res` (the last timed step's chunk results) as
+    <out_dir>/<prefix>chunkNN_<array>.npy, so that two builds run with the same
+    arguments can be compared output for output.  Per chunk: `shape` (status,
+    num_slots, num_values, values_bytes) and, for each of def_levels,
+    rep_levels, values, offsets the chunk has, the array in float64 (levels and
+    string bytes in float32; 64-bit integers and INT96 as their 32-bit words,
+    which float64 holds exactly).  An array too large for its share of the
+    budget is written as `<array>` = the elements at sorted indices drawn from
+    default_rng(0) (the same indices for the same length) and
+    `<array>_blocksum` = the float64 sums of at most DUMP_BLOCKS equal
+    contiguous blocks (the last one shorter), which cover every element."""
+    os.makedirs(out_dir, exist_ok=True)
+    todo = []  # (name, device pointer, bytes, element type, output type)
+    ji = 0
+    for pf, specs, _ in wl.files:
+        for (rg, col) in specs:
+            r = res[ji]
+            name = "%schunk%02d" % (prefix, ji)
+            np.save(os.path.join(out_dir, name + "_shape.npy"),
+                    np.array([r.status, r.num_slots, r.num_values, r.values_bytes], dtype=np.float64))
+            if r.status == 0:
+                if r.def_levels:
+                    todo.append((name + "_def_levels", r.def_levels, r.num_slots, np.uint8, np.float32))
+                if r.rep_levels:
+                    todo.append((name + "_rep_levels", r.rep_levels, r.num_slots, np.uint8, np.float32))
+                if r.offsets:
+                    todo.append((name + "_offsets", r.offsets, (r.num_values + 1) * 8, np.uint32, np.float64))
+                vt = VALUE_VIEW.get(pf.columns[col].desc.physical_type, np.uint8) if r.value_width else np.uint8
+                todo.append((name + "_values", r.values, r.values_bytes, vt,
+                             np.float32 if vt == np.uint8 else np.float64))
+            ji += 1
+    share = DUMP_BUDGET // max(len(todo), 1)
+    for name, ptr, nbytes, et, ot in todo:
+        a = dec.d2h(ptr, nbytes - nbytes % np.dtype(et).itemsize, et)
+        keep = (share - DUMP_BLOCKS * 8) // np.dtype(ot).itemsize
+        if len(a) > keep:
+            m = -(-len(a) // DUMP_BLOCKS)
+            full = len(a) // m
+            sums = a[:full * m].reshape(full, m).sum(axis=1, dtype=np.float64)
+            if full * m < len(a):
+                sums = np.append(sums, a[full * m:].sum(dtype=np.float64))
+            np.save(os.path.join(out_dir, name + "_blocksum.npy"), sums)
+            a = a[np.sort(np.random.default_rng(0).integers(0, len(a), size=max(keep, 1)))]
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(ot))
 
 
 # ---------------------------------------------------------------- CPU baseline
@@ -344,11 +427,14 @@ def split_jobs(jobs, k):
     return [sorted(p) for p in parts if p]
 
 
-def run_workload(wl, decs, args, steps, warmup, barrier, dist, world, rank, cpu_seconds):
+def run_workload(wl, decs, args, steps, warmup, barrier, dist, world, rank, cpu_seconds, dump_dir=None):
     """One workload's line.  decs: the decode contexts (each with its own HIP
     stream); the chunks are dealt over them and decoded concurrently
     (pqg_decode_chunks_async on each, then pqg_sync on each), so one
-    context's level stage overlaps another's values stage."""
+    context's level stage overlaps another's values stage.  dump_dir: where
+    the last timed step's outputs go (dump_outputs).  Without args.full the
+    line holds what the timed steps alone give and the second return value is
+    None."""
     dec = decs[0]
     import pqgpu
     from pqgpu import abi
@@ -406,6 +492,34 @@ def run_workload(wl, decs, args, steps, warmup, barrier, dist, world, rank, cpu_
     barrier()
     for i, (c, j) in where.items():
         res[i] = ress[c][j]
+    if dump_dir:
+        dump_outputs(wl, dec, res, dump_dir, "rank%d_" % rank if world > 1 else "")
+
+    def max_elapsed():
+        if dist is None:
+            return t_end - t_start
+        import torch
+        on_gpu = dist.get_backend() == "nccl"
+        t = torch.tensor([t_end - t_start], dtype=torch.float64, device="cuda" if on_gpu else "cpu")
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        return float(t.item())
+
+    if not args.full:
+        elapsed = max_elapsed()
+        b_in, b_out = io_bytes(wl, res)
+        return {
+            "workload": wl.desc,
+            "value": round(b_out * world / elapsed * steps / 1e9, 3),
+            "unit": "GB/s",
+            "ms_per_step": round(elapsed / steps * 1e3, 4),
+            "steps": steps,
+            "chunks_per_step": n,
+            "bytes_in": b_in,
+            "bytes_out": b_out,
+            "h2d_bytes_per_rank": wl.uploaded,
+            "streams": K,
+            "host_peak_rss_gb": peak_rss_gb(),
+        }, None
     verified = None
     if not args.no_verify:  # the timed path's outputs (the one-context pass below re-allocates context 0's arenas)
         verified = verify(wl, dec, res)
@@ -419,13 +533,7 @@ def run_workload(wl, decs, args, steps, warmup, barrier, dist, world, rank, cpu_
             raise RuntimeError("decode failed: %d" % rc)
         k = L.pqg_last_timings(dec.ctx, tmp, 16)
         stage_acc += np.array([tmp[i] for i in range(1, min(k, 1 + len(STAGES)))])
-    elapsed = t_end - t_start
-    if dist is not None:
-        import torch
-        on_gpu = dist.get_backend() == "nccl"
-        t = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if on_gpu else "cpu")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
+    elapsed = max_elapsed()
     b_in, b_out, alg = account(wl, dec.pages, res1)
     stage_ms = stage_acc / steps
     dev_ms = float(stage_ms.sum())
@@ -597,8 +705,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rows", type=int, default=100_000_000, help="C2 rows per file")
     ap.add_argument("--bits", type=str, default="1,2,4,8,12,16,20")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: verify the outputs, run the instrumented steps (rooflines), K8, "
+                         "the CPU baselines and the sub-results")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="write the last timed step's outputs as DIR/<name>.npy (dump_outputs)")
     ap.add_argument("--configs", type=str, default="c1,c1_1page,c2_run_heavy,c3,c3_gzip,c4,c5",
-                    help="sub-results besides the C2 headline")
+                    help="with --full: sub-results besides the C2 headline")
     ap.add_argument("--sub-steps", type=int, default=5)
     ap.add_argument("--c1-rows", type=int, default=10_000_000)
     ap.add_argument("--c3-rows", type=int, default=200_000_000)
@@ -606,11 +719,14 @@ def main():
     ap.add_argument("--c4-rows", type=int, default=50_000_000)
     ap.add_argument("--c5-rows-per-rg", type=int, default=15_625_000)
     ap.add_argument("--streams", type=int, default=2, help="decode contexts (HIP streams) the chunks are dealt over")
-    ap.add_argument("--no-verify", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=16.0, help="bound on the headline CPU-baseline sample")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-verify", action="store_true", help="with --full: skip the verification")
+    ap.add_argument("--cpu-seconds", type=float, default=16.0,
+                    help="with --full: bound on the headline CPU-baseline sample")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--only", type=str, default="", help="profiling: run one config alone and print its result")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus))  # nothing above touched the GPU
@@ -648,9 +764,10 @@ def main():
             dec.free(d)
         wl.devs = []
 
-    if args.only:  # profiling runs (tools/gpu_profile.sh): one workload, its own JSON line
+    if args.only:  # profiling runs (tools/gpu_steps.sh): one workload, its own JSON line
         w = gen_workload(args.only, args, rank, world)
-        sub, _ = run_workload(w, decs, args, args.steps, args.warmup, barrier, dist, world, rank, 6.0)
+        sub, _ = run_workload(w, decs, args, args.steps, args.warmup, barrier, dist, world, rank, 6.0,
+                              args.dump_outputs)
         if rank == 0:
             print(json.dumps({"only": args.only, "n_gpus": world, **sub}), flush=True)
         release(w)
@@ -658,13 +775,14 @@ def main():
             d.close()
         return
 
-    wl = gen_workload("c2", args, rank, world)
-    head, res = run_workload(wl, decs, args, args.steps, args.warmup, barrier, dist, world, rank, args.cpu_seconds)
-    k8 = k8_c2(dec, wl, res, args) if rank == 0 else None
+    wl = gen_workload("c2", args, rank, world, expected=args.full and not args.no_verify)
+    head, res = run_workload(wl, decs, args, args.steps, args.warmup, barrier, dist, world, rank, args.cpu_seconds,
+                             args.dump_outputs)
+    k8 = k8_c2(dec, wl, res, args) if rank == 0 and args.full else None
     release(wl)
     del wl
     subs = {}
-    for key in [k for k in args.configs.split(",") if k]:
+    for key in [k for k in args.configs.split(",") if k and args.full]:
         w = gen_workload(key, args, rank, world)
         # C1's steps take ~0.2 ms: ten times the steps, so host jitter averages out
         n_steps = args.sub_steps * (10 if key in ("c1", "c1_1page") else 1)
@@ -698,17 +816,21 @@ def main():
                 "parallelism": ("row-group shards: one process per GPU, RG i -> GPU floor(i*N/R), no data-path "
                                 "collective" if world > 1 else "single GPU"),
             },
-            "roofline": head["roofline"],
-            "cpu_baseline": head.get("cpu_baseline"),
-            "cpu_baseline_all_cores": head.get("cpu_baseline_all_cores"),
-            "verified_bit_exact": head.get("verified_bit_exact"),
-            "k8_assemble": k8,
-            "configs": subs,
         }
+        if args.full:
+            out.update({
+                "roofline": head["roofline"],
+                "cpu_baseline": head.get("cpu_baseline"),
+                "cpu_baseline_all_cores": head.get("cpu_baseline_all_cores"),
+                "verified_bit_exact": head.get("verified_bit_exact"),
+                "k8_assemble": k8,
+                "configs": subs,
+            })
         print(json.dumps(out), flush=True)
-        # the same line again, compact, LAST: every config's numbers survive a
-        # truncated stdout tail (the full line above carries the details)
-        print(json.dumps(compact_line(out)), flush=True)
+        if args.full:
+            # the same line again, compact, LAST: every config's numbers survive a
+            # truncated stdout tail (the full line above carries the details)
+            print(json.dumps(compact_line(out)), flush=True)
     for d in decs:
         d.close()
     if dist is not None:

@@ -350,12 +350,15 @@ def config_delta_strings(rows=200_000, encoding=DELTA_BYTE_ARRAY, rows_per_page=
 
 
 def config_c2_family(rows=100_000_000, bits_list=(1, 2, 4, 8, 12, 16, 20), null_frac=0.10, rows_per_page=20000,
-                     seed=2, run_heavy=False):
+                     seed=2, run_heavy=False, workers=1):
     """C2 at every index width: one file per width sharing the null pattern and
     the (masked) index draw.  Index streams: uniform keys
     (bit-packed dominated), or run_heavy: keys repeated in runs of geometric
     length, mean 16 (RLE runs dominate).  Yields (bits, file_bytes, expected)
-    where expected = (def_levels u8[rows], dense int32 values)."""
+    where expected = (def_levels u8[rows], dense int32 values).  workers > 1
+    writes that many widths at a time on host threads (the shared draws are
+    made once, before them; numpy and the writer release the GIL): the same
+    files in the same order, sooner, all held at once."""
     rng = np.random.default_rng(seed)
     defs = (rng.random(rows) >= null_frac).astype(np.uint8)
     nn = int(defs.sum())
@@ -368,14 +371,25 @@ def config_c2_family(rows=100_000_000, bits_list=(1, 2, 4, 8, 12, 16, 20), null_
     else:
         raw = rng.integers(0, 1 << 20, size=nn, dtype=np.int64)
     dict_all = rng.integers(-2**31, 2**31 - 1, size=1 << 20, dtype=np.int64).astype(np.int32)
-    for bits in bits_list:
+
+    def one(bits):
         d = 1 << bits
         idx = raw & (d - 1)
         idx[: min(d, nn)] = np.arange(min(d, nn))
         vals = dict_all[:d][idx]
+        del idx
         col = Column("c2", INT32, vals, repetition=OPTIONAL, encoding=RLE_DICTIONARY, def_levels=defs,
                      rows_per_page=rows_per_page)
-        yield bits, write_file([col], rows), (defs, vals)
+        return bits, write_file([col], rows), (defs, vals)
+
+    if workers > 1:
+        from concurrent.futures import ThreadPoolExecutor
+        lib()  # loaded once, before the threads ask for it
+        with ThreadPoolExecutor(max_workers=workers) as ex:
+            yield from list(ex.map(one, bits_list))
+    else:
+        for bits in bits_list:
+            yield one(bits)
 
 
 C5_ROWS_PER_RG = 15_625_000

@@ -190,7 +190,7 @@ def test_bench_launches_ranks():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--only", "c5",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--full", "--only", "c5",
                           "--c5-rows-per-rg", "20000", "--steps", "2", "--warmup", "1", "--no-cpu"],
                          capture_output=True, text=True, timeout=240, env=env, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]

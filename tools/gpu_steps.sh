@@ -9,12 +9,12 @@
 # steps:
 #   tests[:<pytest -k expr>]   pytest -m gpu (TESTS= files, default tests/)
 #   smoke                      __graft_entry__.smoke()
-#   bench[:<name>]             bench.py $BENCH_ARGS  -> bench_<name>.json
-#   only:<cfg>[:<name>[:<args>]]  bench.py --only <cfg> $ONLY_ARGS [args, commas for spaces] -> only_<name>.out
+#   bench[:<name>]             bench.py --full $BENCH_ARGS  -> bench_<name>.json
+#   only:<cfg>[:<name>[:<args>]]  bench.py --full --only <cfg> $ONLY_ARGS [args, commas for spaces] -> only_<name>.out
 #   probe:<cfg>                tools/probe_jobs.py --only <cfg> $PROBE_ARGS
-#   prof:<cfg>[:<name>[:<args>]]  rocprofv3 --kernel-trace --stats of bench.py --only <cfg> [args, commas
+#   prof:<cfg>[:<name>[:<args>]]  rocprofv3 --kernel-trace --stats of bench.py --full --only <cfg> [args, commas
 #                              for spaces] -> prof_<name>.md
-#   pmc:<cfg>:<C1,C2,...>      one rocprofv3 --pmc pass of bench.py --only <cfg>
+#   pmc:<cfg>:<C1,C2,...>      one rocprofv3 --pmc pass of bench.py --full --only <cfg>
 # env: PQG_LIB (library variant), STEPS (bench steps for only/prof/pmc)
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
@@ -41,17 +41,17 @@ for step in "$@"; do
       run ${TEST_TIMEOUT:-600} pytest python -u -m pytest ${TESTS:-tests} -m gpu -v --timeout 120 --timeout-method thread "${K[@]}"
       rc=$?; tail -3 "$OUT/pytest.out" ;;
     smoke) run 300 smoke python -u -c "import __graft_entry__ as g; g.smoke()"; rc=$? ;;
-    bench) run ${BENCH_TIMEOUT:-900} "bench_${a1:-main}" python -u bench.py $BENCH_ARGS; rc=$? ;;
+    bench) run ${BENCH_TIMEOUT:-900} "bench_${a1:-main}" python -u bench.py --full $BENCH_ARGS; rc=$? ;;
     only)  # only:<cfg>[:<name>[:<extra bench args, commas for spaces>]]
       IFS=: read -r _k _c _n ex <<< "$step"
-      run 400 "only_${a2:-$a1}" python -u bench.py --only "$a1" --steps "$STEPS_N" --warmup 2 $ONLY_ARGS ${ex//,/ }
+      run 400 "only_${a2:-$a1}" python -u bench.py --full --only "$a1" --steps "$STEPS_N" --warmup 2 $ONLY_ARGS ${ex//,/ }
       rc=$? ;;
     probe) run 400 "probe_$a1" python -u tools/probe_jobs.py --only "$a1" $PROBE_ARGS; rc=$? ;;
     prof)  # prof:<cfg>[:<name>[:<extra bench args, commas for spaces>]]
       nm=${a2:-$a1}
       IFS=: read -r _k _c _n ex <<< "$step"
       run 400 "prof_$nm" rocprofv3 --kernel-trace --stats -d "$OUT/prof_$nm" -o run -- \
-        python3 -u bench.py --only "$a1" --steps "$STEPS_N" --warmup 2 --no-cpu --no-verify $ONLY_ARGS ${ex//,/ }
+        python3 -u bench.py --full --only "$a1" --steps "$STEPS_N" --warmup 2 --no-cpu --no-verify $ONLY_ARGS ${ex//,/ }
       rc=$?
       if [ $rc -eq 0 ]; then
         db=$(find "$OUT/prof_$nm" -name "*.db" | head -1)
@@ -62,7 +62,7 @@ for step in "$@"; do
     pmc)
       ctr=${a2//,/ }
       run 300 "pmc_${a1}_${a2//,/_}" rocprofv3 --pmc $ctr --output-format csv -d "$OUT/pmc" -o "${a1}_${a2//,/_}" -- \
-        python3 -u bench.py --only "$a1" --steps 2 --warmup 1 --no-cpu --no-verify $ONLY_ARGS
+        python3 -u bench.py --full --only "$a1" --steps 2 --warmup 1 --no-cpu --no-verify $ONLY_ARGS
       rc=$? ;;
     *) echo "unknown step $step"; exit 2 ;;
   esac
