@@ -20,9 +20,21 @@
 //     read into lanes, then every run and payload granule of the piece is
 //     loaded before the first LDS write), then decodes the piece's blocks
 //     from LDS with no global load in between;
-//   * larger dictionaries are gathered from global memory, software-pipelined
-//     across block pairs: the gathers of pair k + 1 are issued before the
-//     stores of pair k, so no wait for a gather includes stores issued after it.
+//   * the loads of the next piece are issued as soon as the current piece's
+//     descriptors say where it starts, before the current piece's first store,
+//     and stay in registers (PieceLoads) until the piece is staged.  A piece
+//     that opens with single-run blocks decodes up to kFastJ of them in
+//     straight-line code with exactly 8 unguarded stores each (lanes past a
+//     block's end repeat its last value, block_slot), then "lands" the
+//     next piece's loads: the compiler knows how many memory instructions
+//     follow the loads and waits with that count (vmcnt retires in issue
+//     order), so the wait covers none of this piece's stores.  Other pieces
+//     land the loads with a plain wait before their first block;
+//   * larger dictionaries are gathered from global memory; inside the
+//     straight-line blocks the gathers of block k + 1 are issued before the
+//     stores of block k, so the wait for a block's gathers covers no store
+//     issued after them.  Blocks outside (multi-run, past kFastJ) gather and
+//     store block by block.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -147,7 +159,11 @@ int prof_read_dict(unsigned long long* out) {
 
 // Per-wave phase accumulators of diagnostic builds (-DPQG_PROFILE), flushed
 // with one atomic per slot when the wave exits (per-event atomics on one word
-// would serialise the waves and distort what they measure).
+// would serialise the waves and distort what they measure).  Slots of
+// dict_page: 0 staging, 1 issue + blocks + landing, 4 pieces, 5 blocks, 11 per
+// block of the generic loop; 12 pieces whose loads landed behind the head's
+// stores, 13 loads dropped (past the page's end) or issued again, 14 pieces
+// landed with a plain wait, 15 a page's first piece (nothing staged).
 struct DProf {
 #ifdef PQG_PROFILE
   uint64_t a[16] = {0};
@@ -190,8 +206,9 @@ __device__ __forceinline__ void block_out(PieceShared& ps, const PBlock& B, uint
     const uint32_t st = (uint32_t)__builtin_amdgcn_readfirstlane(e.start), src = (uint32_t)__builtin_amdgcn_readfirstlane(e.src);
     if (!(st & kRunBP)) {
       // one RLE run: one lookup
-      const uint32_t x = dict(src < dcount ? src : 0u);
+      uint32_t x = dict(src < dcount ? src : 0u);
       if (src >= dcount) bad = (int64_t)B.v0 < bad ? (int64_t)B.v0 : bad;
+      if (Dict::kGlobal) asm volatile("" : "+v"(x));  // see below
 #pragma unroll
       for (int q = 0; q < 8; q++)
         if ((uint32_t)(lane + 64 * q) < nv) dict_store(out + lane + 64 * q, x);
@@ -251,9 +268,166 @@ __device__ __forceinline__ void block_out(PieceShared& ps, const PBlock& B, uint
   uint32_t val[8];
 #pragma unroll
   for (int q = 0; q < 8; q++) val[q] = dict((uint32_t)(lane + 64 * q) < nv ? key[q] : 0u);
+  // Gathers are waited for here, outside the guarded stores: a gather first
+  // used under a branch is still outstanding, to the compiler, on the path
+  // around the branch, and every later join (the piece loop's among them)
+  // then waits with that gather's count -- draining the stores behind it.
+  if (Dict::kGlobal) {
+#pragma unroll
+    for (int q = 0; q < 8; q++) asm volatile("" : "+v"(val[q]));
+  }
 #pragma unroll
   for (int q = 0; q < 8; q++)
     if ((uint32_t)(lane + 64 * q) < nv) dict_store(out + lane + 64 * q, val[q]);
+}
+
+// The loads of one piece, in registers from their issue to the piece's staging.
+struct PieceLoads {
+  u32x4_t q;            // lane's block descriptor
+  u32x4_t rg[kPRunGr];  // run entries
+  u32x4_t pg[kPG];      // payload window
+};
+
+// Issue the loads of the piece at block kb, run rcur, payload offset pos.
+// Unconditional, every address clamped inside the tables and the stream (a
+// lane past the last block reads the last descriptor; a granule past the
+// stream reads the stream's first): a piece position past the page's end is a
+// wasted round of loads, never a fault.
+// kTag names the call site in the code, so that the compiler does not hoist
+// the loads of dict_page's alternatives into one place before them.
+template <int kTag>
+__device__ __forceinline__ void piece_issue(PieceLoads& L, const gcu8 sp, const int64_t n, const PQG_G RunEnt* runs,
+                                            const PQG_G BlockDesc* blks, const int nb_all, const int kb,
+                                            const uint32_t rcur, const int64_t pos, const int lane) {
+  asm volatile("; piece loads, %0 blocks ahead of their landing" ::"n"(kTag));
+  const uintptr_t pa = (uintptr_t)sp;
+  // past the last block the loads stay (their number must not depend on the
+  // path) but every lane reads one granule: 6 lines instead of 6 KiB
+  const bool live = kb < nb_all;
+  L.q = *(const PQG_G u32x4_t*)(uintptr_t)(blks + (kb + lane < nb_all ? kb + lane : nb_all - 1));
+  const uintptr_t ra_al = (uintptr_t)(runs + rcur) & ~(uintptr_t)15;
+#pragma unroll
+  for (int k = 0; k < kPRunGr; k++)
+    L.rg[k] = *(const PQG_G u32x4_t*)(ra_al + (live ? 16 * (uintptr_t)(lane + 64 * k) : 0));
+  const int64_t plo = pos - (int64_t)((pa + (uintptr_t)pos) & 15);  // 16-byte aligned address
+#pragma unroll
+  for (int k = 0; k < kPG; k++) {  // zeroed past the stream's end when staged (mask_tail)
+    const int64_t at = plo + 16 * (int64_t)(lane + 64 * k);
+    const uintptr_t a = live && at < n ? (uintptr_t)(sp + at) : (pa & ~(uintptr_t)15);
+#if PQG_DICT_NT_IN
+    L.pg[k] = __builtin_nontemporal_load((const PQG_G u32x4_t*)a);  // index bytes: read once
+#else
+    L.pg[k] = *(const PQG_G u32x4_t*)a;
+#endif
+  }
+}
+
+// To re-read what the compiler made of this (after a compiler update, or a
+// change to dict_page): `hipcc --offload-arch=gfx950 --cuda-device-only -S`
+// this file; in k_dict4 the comments "piece loads, J blocks ahead" / "piece
+// loads landed behind J blocks" bracket each alternative, and the vmcnt waits
+// between them should count down from 5 + 8 J (LDS dictionary), with none
+// between a landing and the LDS writes of the staging.
+//
+// Wait for the loads of L here: a use of every register, so the compiler
+// places the s_waitcnt with the count of memory instructions issued since the
+// loads on this path.  kTag keeps the copies on different paths apart (merged
+// into the join, they would wait with the smallest count of the paths, 0).
+template <int kTag>
+__device__ __forceinline__ void piece_land(PieceLoads& L) {
+  asm volatile("" : "+v"(L.q));
+#pragma unroll
+  for (int k = 0; k < kPRunGr; k++) asm volatile("" : "+v"(L.rg[k]));
+#pragma unroll
+  for (int k = 0; k < kPG; k++) asm volatile("" : "+v"(L.pg[k]));
+  asm volatile("; piece loads landed behind %0 blocks" ::"n"(kTag));
+}
+
+// Value of a single-run block that lane `lane` handles in round q: value
+// lane + 64 q, or the block's last one where that is past the block (blocks of
+// wide indices hold fewer than kHBlock values, 400 at b = 20, and a page's last
+// block is cut at its count).  The lanes past the end look the last value up
+// again and store it again, so every block is 8 lookups and 8 stores with no
+// guard and no branch: the number of memory instructions is known to the
+// compiler, which the wait counts of the landing and of the gathers need.
+__device__ __forceinline__ uint32_t block_slot(int lane, int q, uint32_t nv) {
+  const uint32_t j = (uint32_t)(lane + 64 * q);
+  return j < nv ? j : nv - 1;
+}
+
+// The keys of a single-run block of nv >= 1 values, clamped and checked, then
+// looked up: 8 lookups per lane, no store.  An RLE run takes the same path
+// with every key its value, so that the number of memory instructions of the
+// block does not depend on the run's kind.
+template <class Dict>
+__device__ __forceinline__ void full_block_lookup(PieceShared& ps, uint32_t bv0, uint32_t nv, uint32_t rl, uint32_t mask,
+                                                  int w, int64_t plo8, int lane, uint32_t dcount, const Dict& dict,
+                                                  int64_t& bad, uint32_t (&val)[8]) {
+  const RunEnt e = ps.runs[rl];
+  const uint32_t st = (uint32_t)__builtin_amdgcn_readfirstlane(e.start), src = (uint32_t)__builtin_amdgcn_readfirstlane(e.src);
+  const bool bp = (st & kRunBP) != 0;
+  const uint32_t rb0 = (uint32_t)((int64_t)src * 8 - plo8) + (bv0 - (st & ~kRunBP)) * (uint32_t)w;
+  uint32_t key[8], mx = 0;
+#pragma unroll
+  for (int q = 0; q < 8; q++) {
+    const uint32_t j = block_slot(lane, q, nv);
+    const uint32_t rb = rb0 + j * (uint32_t)w;
+    const uint32_t d = bp ? rb >> 5 : 0u;
+    const uint32_t bits = __builtin_amdgcn_alignbit(ps.stage[d + 1], ps.stage[d], rb & 31) & mask;
+    key[q] = bp ? bits : src;
+    mx = key[q] > mx ? key[q] : mx;
+  }
+  if (__ballot(mx >= dcount)) {
+#pragma unroll
+    for (int q = 0; q < 8; q++) {
+      const uint32_t j = block_slot(lane, q, nv);
+      if (key[q] >= dcount) bad = (int64_t)(bv0 + j) < bad ? (int64_t)(bv0 + j) : bad;
+      key[q] = key[q] < dcount ? key[q] : 0u;
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 8; q++) val[q] = dict(key[q]);
+}
+// its 8 stores: no guard, no branch
+__device__ __forceinline__ void full_block_store(PQG_G uint32_t* out, uint32_t nv, int lane, const uint32_t (&val)[8]) {
+#pragma unroll
+  for (int q = 0; q < 8; q++) dict_store(out + block_slot(lane, q, nv), val[q]);
+}
+
+// Blocks per piece decoded in straight-line code before the next piece's
+// loads are landed (the wait then has 8 kFastJ stores, and with a global
+// dictionary the gathers, behind the loads it waits for).
+#ifndef PQG_DICT_FASTJ
+#define PQG_DICT_FASTJ 3
+#endif
+constexpr int kFastJ = PQG_DICT_FASTJ;
+
+// The first J blocks of a piece, all single-run blocks (v0 / nvl / r0: the
+// descriptor registers, block k in lane k): the lookups of block k + 1 are
+// issued before the stores of block k, then the next piece's loads land.
+template <int J, class Dict>
+__device__ __forceinline__ void piece_head(PieceShared& ps, uint32_t v0, uint32_t nvl, uint32_t r0, uint32_t rbase,
+                                           uint32_t mask, int w, int64_t plo8, int lane, PQG_G uint32_t* out32,
+                                           uint32_t vfirst, uint32_t dcount, const Dict& dict, int64_t& bad,
+                                           PieceLoads& nx) {
+  uint32_t val[8], nval[8];
+  full_block_lookup(ps, (uint32_t)__builtin_amdgcn_readlane((int)v0, 0), (uint32_t)__builtin_amdgcn_readlane((int)nvl, 0),
+                    (uint32_t)__builtin_amdgcn_readlane((int)r0, 0) - rbase, mask, w, plo8, lane, dcount, dict, bad, val);
+#pragma unroll
+  for (int k = 0; k < J; k++) {
+    if (k + 1 < J)
+      full_block_lookup(ps, (uint32_t)__builtin_amdgcn_readlane((int)v0, k + 1),
+                        (uint32_t)__builtin_amdgcn_readlane((int)nvl, k + 1),
+                        (uint32_t)__builtin_amdgcn_readlane((int)r0, k + 1) - rbase, mask, w, plo8, lane, dcount, dict,
+                        bad, nval);
+    full_block_store(out32 + ((uint32_t)__builtin_amdgcn_readlane((int)v0, k) - vfirst),
+                     (uint32_t)__builtin_amdgcn_readlane((int)nvl, k), lane, val);
+    if (k + 1 < J) {
+#pragma unroll
+      for (int q = 0; q < 8; q++) val[q] = nval[q];
+    }
+  }
+  piece_land<J>(nx);
 }
 
 // Decode one page (or a part of a big page): keys piece by piece, looked up
@@ -281,41 +455,89 @@ __device__ __forceinline__ int64_t dict_page(PieceShared& ps, const gcu8 sp, con
   int64_t pos = (d0.w & 0xffffu) ? (int64_t)d0.z : 0;  // stream offset of the payload window (before alignment)
   const uint32_t vfirst = d0.x;         // the first block's value 0: out[0]
   PQG_G uint32_t* const out32 = (PQG_G uint32_t*)out;
-  while (kb < nb_all) {
-    PQG_DT(ta);
-    // ---- one round of loads: descriptors, run entries, payload window
-    // (unconditional: a lane past the last block reads the last one, then
-    // takes the empty descriptor; a load under a branch is waited for inside it)
-    uint4 q = ldg16((uintptr_t)(blks + (kb + lane < nb_all ? kb + lane : nb_all - 1)));
-    const uintptr_t ra = (uintptr_t)(runs + rcur);
-    const uintptr_t ra_al = ra & ~(uintptr_t)15;
-    const int rskew = (int)((ra - ra_al) >> 3);  // 0 or 1 entry before rcur
-    uint4 rg[kPRunGr];
-#pragma unroll
-    for (int k = 0; k < kPRunGr; k++) rg[k] = ldg16(ra_al + 16 * (uintptr_t)(lane + 64 * k));
-    const int64_t plo = pos - (int64_t)((pa + (uintptr_t)pos) & 15);  // 16-byte aligned address
-    uint4 pg[kPG];
-#pragma unroll
-    for (int k = 0; k < kPG; k++) {  // unconditional loads (see dbp_restage): zeroed when stored
-      const int64_t at = plo + 16 * (int64_t)(lane + 64 * k);
-#if PQG_DICT_NT_IN
-      pg[k] = ldg16_nt(at < n ? (uintptr_t)(sp + at) : (pa & ~(uintptr_t)15));  // index bytes: read once
-#else
-      pg[k] = ldg16(at < n ? (uintptr_t)(sp + at) : (pa & ~(uintptr_t)15));
-#endif
+  // One round per piece: issue the loads of the piece at (kb, rcur, pos), decode
+  // the blocks of the piece staged by the round before (their stores go out
+  // behind those loads), land the loads, then stage the loaded piece.  Each
+  // alternative below issues and lands the loads itself: no path, not even
+  // one the compiler only thinks possible, then leads from an issue around a
+  // landing to the staging code, where it would put a wait with the count of
+  // "just issued" -- behind all the stores.  The loads are consumed in the
+  // round that issued them, so no register of L is carried around the loop.
+  uint32_t v0 = 0, r0 = 0, nr = 0;     // the staged piece's descriptors: lane k holds block k
+  uint32_t nvl = 0;                    // values of block k
+  int m = 0, nf = 0;                   // its blocks (0: none staged); the leading single-run ones
+  int64_t plo8 = 0;                    // bit address of its payload window
+  uint32_t rbase = 0;                  // run index of ps.runs[0]
+  for (;;) {
+    if (kb >= nb_all) pf.add(13, 1);  // loads past the page's (part's) last block: never staged
+    PQG_DT(tb);
+    PieceLoads L;
+    int k0 = 0;
+    if (nf >= kFastJ) {
+      piece_issue<kFastJ>(L, sp, n, runs, blks, nb_all, kb, rcur, pos, lane);
+      piece_head<kFastJ>(ps, v0, nvl, r0, rbase, mask, w, plo8, lane, out32, vfirst, dcount, dict, bad, L);
+      k0 = kFastJ;
+      pf.add(12, 1);
+    } else if (kFastJ > 1 && nf == kFastJ - 1) {
+      constexpr int J1 = kFastJ > 1 ? kFastJ - 1 : 1;
+      piece_issue<J1>(L, sp, n, runs, blks, nb_all, kb, rcur, pos, lane);
+      piece_head<J1>(ps, v0, nvl, r0, rbase, mask, w, plo8, lane, out32, vfirst, dcount, dict, bad, L);
+      k0 = J1;
+      pf.add(12, 1);
+    } else {
+      // the page's first piece, a window loaded again (m = 0), or a piece
+      // that opens with a partial or multi-run block: a plain wait
+      piece_issue<0>(L, sp, n, runs, blks, nb_all, kb, rcur, pos, lane);
+      piece_land<0>(L);
+      pf.add(m ? 14 : 15, 1);
     }
+    // ---- the staged piece's other blocks
+    for (int k = k0; k < m; k++) {
+      PQG_DT(tp0);
+      const uint32_t bv0 = (uint32_t)__builtin_amdgcn_readlane((int)v0, k);
+      const uint32_t brl = (uint32_t)__builtin_amdgcn_readlane((int)r0, k) - rbase;
+      if (k < nf) {
+        uint32_t val[8];
+        const uint32_t bnv = (uint32_t)__builtin_amdgcn_readlane((int)nvl, k);
+        full_block_lookup(ps, bv0, bnv, brl, mask, w, plo8, lane, dcount, dict, bad, val);
+        full_block_store(out32 + (bv0 - vfirst), bnv, lane, val);
+      } else {
+        PBlock B;
+        B.on = true;
+        B.v0 = bv0;
+        const uint32_t nx = (uint32_t)__builtin_amdgcn_readlane((int)v0, k + 1);
+        B.v1 = nx < end_all ? nx : end_all;
+        B.rl = brl;
+        B.nr = (uint32_t)__builtin_amdgcn_readlane((int)nr, k);
+        block_out(ps, B, mask, w, plo8, lane, out32 + (B.v0 - vfirst), dcount, dict, bad);
+      }
+      PQG_DT(tp2);
+      pf.add(11, tp2 - tp0);
+    }
+    __builtin_amdgcn_wave_barrier();
+    pf.add(5, (uint64_t)m);
+    PQG_DT(ta);
+    pf.add(1, ta - tb);
+    if (kb >= nb_all) break;
+    // ---- stage the piece: descriptors in lanes (a lane past the last block
+    // takes the empty descriptor), runs and payload window into LDS
+    const uintptr_t ra = (uintptr_t)(runs + rcur);
+    const int rskew = (int)((ra & 15) >> 3);  // 0 or 1 entry before rcur
+    const int64_t plo = pos - (int64_t)((pa + (uintptr_t)pos) & 15);  // 16-byte aligned address
 #pragma unroll
-    for (int k = 0; k < kPRunGr; k++) sts16(lds_ptr(ps.runs) + 2 * (lane + 64 * k), rg[k]);
+    for (int k = 0; k < kPRunGr; k++) *(PQG_L u32x4_t*)(lds_ptr(ps.runs) + 2 * (lane + 64 * k)) = L.rg[k];
 #pragma unroll
     for (int k = 0; k < kPG; k++) {
       const int64_t at = plo + 16 * (int64_t)(lane + 64 * k);
-      sts16(lds_ptr(ps.stage) + 4 * (lane + 64 * k), mask_tail(pg[k], at, n));
+      sts16(lds_ptr(ps.stage) + 4 * (lane + 64 * k), mask_tail(make_uint4(L.pg[k].x, L.pg[k].y, L.pg[k].z, L.pg[k].w), at, n));
     }
+    uint4 q = make_uint4(L.q.x, L.q.y, L.q.z, L.q.w);
     if (kb + lane >= nb_all) q = make_uint4(0xffffffffu, 0u, 0u, 0u);
-    const uint32_t v0 = q.x, r0 = q.y, lo = q.z, nbytes = q.w & 0xffffu, nr = q.w >> 16;
+    v0 = q.x, r0 = q.y, nr = q.w >> 16;
+    const uint32_t lo = q.z, nbytes = q.w & 0xffffu;
     __builtin_amdgcn_wave_barrier();
-    PQG_DT(tb);
-    pf.add(0, tb - ta);
+    PQG_DT(tc);
+    pf.add(0, tc - ta);
     pf.add(4, 1);
     // ---- the piece: leading blocks whose runs and payload were staged
     const bool need = v0 < end_all;
@@ -325,33 +547,25 @@ __device__ __forceinline__ int64_t dict_page(PieceShared& ps, const gcu8 sp, con
     const bool fits = lane < kPBlocks && need && r0 >= rcur && (r0 + nr - rcur) <= run_room &&
                       (!hasp || ((int64_t)lo >= plo && (int64_t)lo + nbytes <= stage_end));
     const uint64_t fm = __ballot(fits);
-    const int m = (int)__builtin_ctzll(~fm);  // fm bit 63 is never set
+    m = (int)__builtin_ctzll(~fm);  // fm bit 63 is never set
     if (m == 0) {
       if (!__builtin_amdgcn_readfirstlane((int)need)) break;  // block kb starts at or past count
-      // the window missed block kb's payload: restage at it (never twice in a row)
+      // the window missed block kb's payload: load again at it (never twice in a row)
       pos = (int64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)lo);
+      nf = 0;  // nothing staged: the next round only loads
+      pf.add(13, 1);
       continue;
     }
-    const int64_t plo8 = plo * 8;
-    // ---- blocks of the piece
-    for (int k = 0; k < m; k++) {
-      PQG_DT(tp0);
-      PBlock B;
-      B.on = true;
-      B.v0 = (uint32_t)__builtin_amdgcn_readlane((int)v0, k);
-      const uint32_t nx = (uint32_t)__builtin_amdgcn_readlane((int)v0, k + 1);
-      B.v1 = nx < end_all ? nx : end_all;
-      B.rl = (uint32_t)__builtin_amdgcn_readlane((int)r0, k) - rcur + (uint32_t)rskew;
-      B.nr = (uint32_t)__builtin_amdgcn_readlane((int)nr, k);
-      block_out(ps, B, mask, w, plo8, lane, out32 + (B.v0 - vfirst), dcount, dict, bad);
-      PQG_DT(tp2);
-      pf.add(11, tp2 - tp0);
-    }
-    __builtin_amdgcn_wave_barrier();
-    PQG_DT(tc);
-    pf.add(1, tc - tb);
-    pf.add(5, (uint64_t)m);
-    // ---- the next piece: block kb + m (lane m's descriptor)
+    plo8 = plo * 8;
+    rbase = rcur - (uint32_t)rskew;
+    // leading single-run blocks (lane k + 1 holds block k's end)
+    const uint32_t nxv = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v0, 0x130, 0xf, 0xf, true);  // wave_shl:1
+    nvl = (nxv < end_all ? nxv : end_all) - v0;  // the block's values (cut at the page's count)
+    const bool full = lane < m && nr == 1 && nvl >= 1 && nvl <= (uint32_t)kHBlock;
+    nf = (int)__builtin_ctzll(~__ballot(full));  // <= m <= 63
+    // ---- the next piece: block kb + m (lane m's descriptor).  Its position
+    // depends on the descriptors alone, so the next round loads it ahead of
+    // every store of this piece.
     const uint32_t hi = hasp ? lo + nbytes : 0u;
     const uint32_t phi = (uint32_t)__builtin_amdgcn_readlane((int)ldpp_incl_max_u32(hi), m - 1);
     kb += m;
