@@ -205,8 +205,37 @@ struct JobDev {
   int64_t run_used, blk_used;  // run-table / block-index entries the pages need (k_page_list)
   // ---- values-stage work items of the job (k_part_plan): parts [item_base, item_base + n_items)
   int64_t item_base;
-  int32_t n_items, pad2;
+  int32_t n_items;
+  int32_t second_dict;     // K1: second ok-rank of a dictionary page (k_cand_link)
+  // ---- k_finalize: first page with a read error / a decode error (INT32_MAX: none), and the job's
+  // blocks that have added theirs; k_nn_scan_sums: the blocks' sums so far, and the blocks that have
+  // added theirs.  The block that arrives last finishes the job.  All reset by k_page_list.
+  int32_t fin_read, fin_dec, fin_done, nn_done;
+  unsigned long long nn_acc, parts_acc;
 };
+
+// The per-chunk bookkeeping kernels (k_page_chain, k_page_list, k_nn_scan,
+// k_finalize) run one workgroup per block of kChunkBlock consecutive pages
+// of a chunk (grid.x: the job, grid.y: the block).  A block needs the sum of
+// everything before it in its chunk: k_page_chain and k_page_list read the
+// earlier pages' numbers again (one load per earlier block and lane, all in
+// flight together), k_nn_scan takes them from k_nn_scan_sums.  A chunk of more
+// than kChunkBlocks blocks is walked by its block 0 alone, in rounds.  What is
+// done once per job after all of its blocks (k_nn_scan_sums, k_finalize) is
+// done by the block that arrives last at a counter of the job: no block waits.
+constexpr int kChunkBlock = 1024;
+constexpr int kChunkBlocks = 32;
+// k_nn_scan_sums -> k_nn_scan (pqg_levels.hip)
+struct NnSums {
+  int64_t nn, parts;
+};
+struct NnJob {
+  int64_t base;  // first part slot
+  int64_t res;   // reserved slots (even when they do not fit)
+  int32_t cap;   // out of capacity: no parts
+  int32_t np;    // the job's pages as k_nn_scan_sums saw them (the status may change here); -1: the general path
+};
+
 
 // ---------------------------------------------------------------------------
 // Big pages (parquet-go's own writer puts a whole column chunk in ONE data

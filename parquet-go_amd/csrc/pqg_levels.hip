@@ -12,7 +12,8 @@
 //   K3b k_hybrid_walk    one LANE per value stream: the serial run-header walk
 //                        writes a run table and a block index for the values
 //                        kernels (pqg_hybrid.h)
-//   K3d k_nn_scan        per chunk: value offsets = exclusive scan of notNull
+//   K3d k_nn_scan_sums, k_nn_scan
+//                        per 1024 pages of a chunk: value offsets = exclusive scan of notNull
 //                        (readPageData chunk_reader.go:380-402) and the
 //                        dictionary page (page_dict.go:30-64)
 #include <hip/hip_runtime.h>
@@ -578,137 +579,154 @@ __device__ void plan_split_pages(JobDev& job, const PageDev* pp, const HStream* 
 __device__ void plan_parts_from(JobDev& job, int np, const PageDev* pp, const HStream* streams, const BlockDesc* blks,
                                 PartRec* parts, int64_t base);
 
-// Jobs of <= kNnFastSeg x 1024 pages: one read of each page's fields (kept in
-// registers), the notNull and part-count scans together, one write pass.
-constexpr int kNnFastSeg = 12;
+// The notNull scan and the parts of a job, one workgroup per kChunkBlock pages
+// (grid.x: the job, grid.y: the block), in two launches:
+//   k_nn_scan_sums  every block's sums of notNull and of part counts; the job's
+//                   last block: the totals, the capacity checks and the job's part
+//                   slots (one atomicAdd per job: a job's parts stay contiguous)
+//   k_nn_scan       value offsets and parts of the block's pages, from the sums
+//                   of the blocks before it
+// A job of more than gridDim.y blocks is left to block 0 of k_nn_scan, which
+// walks it alone (the general path below).
+__device__ __forceinline__ int nn_pages(const JobDev& job) {
+  const int np = job.num_pages < job.page_cap ? job.num_pages : job.page_cap;
+  return job.status == kCAPACITY ? 0 : np;
+}
+
+// Page i's notNull, part count (part_n) and values stage, from one read of its
+// fields (unconditional loads, the index clamped: a guarded load would be
+// waited for at its branch join); a big hybrid page reads its stream.
+__device__ __forceinline__ void nn_page_counts(const PageDev* pp, int i, int np, const HStream* streams, int32_t* nn,
+                                               int32_t* kv, int32_t* vmode) {
+  const PageDev& pg = pp[i < np ? i : np - 1];
+  const int32_t f_type = pg.page_type, f_nn = pg.not_null, f_rs = pg.read_status, f_ds = pg.decode_status,
+                f_enc = pg.encoding, vm = pg.vmode;
+  *nn = *kv = 0;
+  *vmode = vm;
+  if (i >= np) return;
+  const bool data = f_type == 0 || f_type == 3;
+  *nn = data ? f_nn : 0;
+  int32_t k = 0;
+  if (!data || vm < 0) k = 0;
+  else if (f_rs != kOK || f_ds != kOK || vm == 3) k = 1;
+  else if (vm == 2 && f_enc != 0 && f_enc != 8) k = 1;
+  else if (f_nn <= kSplitMin) k = 1;
+  else {
+    int64_t c;
+    bool h;
+    k = (int32_t)part_n(pp[i], streams, &c, &h);
+  }
+  *kv = k;
+}
+
+__global__ void __launch_bounds__(1024) k_nn_scan_sums(JobDev* jobs, PageDev* pages, uint8_t* scratch,
+                                                       const HStream* streams, NnSums* sums, NnJob* njobs, int* ctr,
+                                                       int64_t parts_cap) {
+  __shared__ int64_t part[17];
+  const int j = blockIdx.x, y = blockIdx.y;
+  JobDev& job = jobs[j];
+  // (the job's status is written below, after every block of the job has read it)
+  const int np = nn_pages(job);
+  const int nblk = (np + kChunkBlock - 1) / kChunkBlock;
+  const bool spread = nblk <= (int)gridDim.y, mine = spread && y < nblk;
+  int64_t ntot = 0, ktot = 0;
+  if (mine) {
+    int32_t nn, kv, vm;
+    nn_page_counts(pages + job.page_base, y * kChunkBlock + (int)threadIdx.x, np, streams, &nn, &kv, &vm);
+    block_excl_scan<1024>(nn, &ntot, part);
+    block_excl_scan<1024>(kv, &ktot, part);
+  }
+  if (threadIdx.x != 0) return;
+  if (mine) {
+    sums[(size_t)j * gridDim.y + y] = NnSums{ntot, ktot};
+    atomicAdd(&job.nn_acc, (unsigned long long)ntot);
+    atomicAdd(&job.parts_acc, (unsigned long long)ktot);
+  }
+  // the block of the job that arrives last: the totals, the capacity checks
+  // and the job's part slots (one atomicAdd per job: a job's parts stay contiguous)
+  __threadfence();
+  if (atomicAdd(&job.nn_done, 1) != (int)gridDim.y - 1) return;
+  __threadfence();
+  if (j == 0) ctr[kCtrPartsCap] = (int)(parts_cap < INT32_MAX ? parts_cap : INT32_MAX);
+  if (!spread) {
+    njobs[j] = NnJob{0, 0, 0, -1};  // k_nn_scan's general path
+    return;
+  }
+  const int64_t carry = (int64_t)atomicAdd(&job.nn_acc, 0ull), parts_tot = (int64_t)atomicAdd(&job.parts_acc, 0ull);  // reads
+  const bool fail0 = job.status == kCAPACITY;
+  int cap = nn_job_tail(job, pages, scratch, np, carry, fail0);
+  int64_t base = 0;
+  if (!cap) {
+    base = atomicAdd(ctr + kCtrItems, (int)parts_tot);
+    if (base + parts_tot > parts_cap) {
+      job.status = kCAPACITY;
+      cap = 1;
+    }
+  }
+  job.item_base = base;
+  job.n_items = cap ? 0 : (int32_t)parts_tot;
+  njobs[j] = NnJob{base, fail0 ? 0 : parts_tot, cap, np};
+}
 
 __global__ void __launch_bounds__(1024) k_nn_scan(JobDev* jobs, PageDev* pages, uint8_t* scratch,
                                                   const HStream* streams, const BlockDesc* blks, int* ctr,
-                                                  PartRec* parts, int64_t parts_cap) {
+                                                  PartRec* parts, int64_t parts_cap, const NnSums* sums,
+                                                  const NnJob* njobs) {
   __shared__ int64_t part[17];
   __shared__ int s_cap;
   JobDev& job = jobs[blockIdx.x];
-  int np = job.num_pages < job.page_cap ? job.num_pages : job.page_cap;
-  if (job.status == kCAPACITY) np = 0;
-  if (np <= kNnFastSeg * 1024) {
-    __shared__ int64_t s_base, s_res;
-    __shared__ int s_big[256];
-    __shared__ int64_t s_boff[256];
+  const int y = blockIdx.y;
+  const NnJob nj = njobs[blockIdx.x];
+  if (nj.np >= 0) {
+    __shared__ int s_big[kChunkBlock];
+    __shared__ int64_t s_boff[kChunkBlock];
     __shared__ int s_nbig;
-    const int seg = (np + 1023) / 1024;
-    const int s0 = (int)threadIdx.x * seg;
+    const int np = nj.np;
+    if (nj.cap) {  // a reservation past the table: its slots inside the table hold no part
+      for (int64_t k = nj.base + (int64_t)y * 1024 + threadIdx.x; k < nj.base + nj.res && k < parts_cap;
+           k += (int64_t)gridDim.y * 1024)
+        parts[k].vmode = -1;
+    }
+    if (y * kChunkBlock >= np) return;
     PageDev* pp = pages + job.page_base;
-    int32_t nnv[kNnFastSeg], kv[kNnFastSeg];
-    int8_t vm[kNnFastSeg];
-    int64_t nsum = 0, ksum = 0;
-    // the fields first, with unconditional loads (clamped page index: a
-    // guarded load would be waited for at its branch join), then the counts
-    int32_t f_type[kNnFastSeg], f_nn[kNnFastSeg], f_rs[kNnFastSeg], f_ds[kNnFastSeg], f_enc[kNnFastSeg];
-#pragma unroll
-    for (int j = 0; j < kNnFastSeg; j++) {
-      const int i = np > 0 ? (s0 + j < np ? s0 + j : np - 1) : 0;
-      const PageDev& pg = pp[i];
-      f_type[j] = pg.page_type;
-      f_nn[j] = pg.not_null;
-      f_rs[j] = pg.read_status;
-      f_ds[j] = pg.decode_status;
-      f_enc[j] = pg.encoding;
-      vm[j] = (int8_t)pg.vmode;
+    int64_t run = 0, koff = 0;  // the blocks before this one
+    for (int q = 0; q < y; q++) {
+      const NnSums t = sums[(size_t)blockIdx.x * gridDim.y + q];
+      run += t.nn;
+      koff += t.parts;
     }
-#pragma unroll
-    for (int j = 0; j < kNnFastSeg; j++) {
-      nnv[j] = kv[j] = 0;
-      if (j < seg && s0 + j < np) {
-        const bool data = f_type[j] == 0 || f_type[j] == 3;
-        nnv[j] = data ? f_nn[j] : 0;
-        // part_n (below) from the fields: big hybrid pages read their stream
-        int32_t k = 0;
-        if (!data || vm[j] < 0) k = 0;
-        else if (f_rs[j] != kOK || f_ds[j] != kOK || vm[j] == 3) k = 1;
-        else if (vm[j] == 2 && f_enc[j] != 0 && f_enc[j] != 8) k = 1;
-        else if (f_nn[j] <= kSplitMin) k = 1;
-        else {
-          int64_t c;
-          bool h;
-          k = (int32_t)part_n(pp[s0 + j], streams, &c, &h);
-        }
-        kv[j] = k;
-      }
-      nsum += nnv[j];
-      ksum += kv[j];
-    }
-    int64_t carry, ktot;
-    int64_t run = block_excl_scan<1024>(nsum, &carry, part);
-    int64_t koff = block_excl_scan<1024>(ksum, &ktot, part);
-    const bool fail0 = job.status == kCAPACITY;
-    if (threadIdx.x == 0) {
-      int cap = nn_job_tail(job, pages, scratch, np, carry, fail0);
-      int64_t base = 0;
-      if (!cap) {
-        base = atomicAdd(ctr + kCtrItems, (int)ktot);
-        if (base + ktot > parts_cap) {
-          job.status = kCAPACITY;
-          cap = 1;
-        }
-      }
-      job.item_base = base;
-      job.n_items = cap ? 0 : (int32_t)ktot;
-      s_base = base;
-      s_cap = cap;
-      s_nbig = 0;
-      s_res = fail0 ? 0 : ktot;  // reserved slots (even when they do not fit)
-      if (blockIdx.x == 0) ctr[kCtrPartsCap] = (int)(parts_cap < INT32_MAX ? parts_cap : INT32_MAX);
-    }
-    __syncthreads();
-    if (s_cap) {  // a reservation past the table: its slots inside the table hold no part
-      for (int64_t k = s_base + threadIdx.x; k < s_base + s_res && k < parts_cap; k += 1024) parts[k].vmode = -1;
-    }
+    const int i = y * kChunkBlock + (int)threadIdx.x;
+    int32_t nn, kv, vm;
+    nn_page_counts(pp, i, np, streams, &nn, &kv, &vm);
+    int64_t tot;
+    run += block_excl_scan<1024>(nn, &tot, part);
+    koff += block_excl_scan<1024>(kv, &tot, part);
     // value offsets (always: the later stages read them), then the parts
-#pragma unroll
-    for (int j = 0; j < kNnFastSeg; j++)
-      if (j < seg && s0 + j < np) {
-        pp[s0 + j].value_offset = run;
-        run += nnv[j];
-      }
-    if (s_cap) return;
-    const int64_t base = s_base;
-    bool more = false;
-#pragma unroll
-    for (int j = 0; j < kNnFastSeg; j++) {
-      if (j < seg && s0 + j < np) {
-        if (kv[j] == 1) {
-          PartRec r;
-          r.pidx = (int32_t)(job.page_base + s0 + j);
-          r.p = 0;
-          r.np = 1;
-          r.v0 = 0;
-          r.b0 = 0;
-          r.vmode = vm[j];
-          r.chars = r.cstart = r.prel = 0;
-          parts[base + koff] = r;
-        } else if (kv[j] > 1) {
-          const int slot = atomicAdd(&s_nbig, 1);
-          if (slot < 256) {
-            s_big[slot] = s0 + j;
-            s_boff[slot] = koff;
-          } else {
-            more = true;
-          }
-        }
-        koff += kv[j];
-      }
-    }
-    const bool any_more = __syncthreads_or(more);
-    const int nbig = s_nbig < 256 ? s_nbig : 256;
-    if (!any_more) {
-      plan_split_pages(job, pp, streams, blks, parts, base, nbig, s_big, s_boff);
-      return;
-    }
-    // more than 256 split pages: the general planner below writes every part again
+    if (i < np) pp[i].value_offset = run;
+    if (nj.cap) return;
+    if (threadIdx.x == 0) s_nbig = 0;
     __syncthreads();
-    plan_parts_from(job, np, pp, streams, blks, parts, base);
+    if (kv == 1) {
+      PartRec r;
+      r.pidx = (int32_t)(job.page_base + i);
+      r.p = 0;
+      r.np = 1;
+      r.v0 = 0;
+      r.b0 = 0;
+      r.vmode = vm;
+      r.chars = r.cstart = r.prel = 0;
+      parts[nj.base + koff] = r;
+    } else if (kv > 1) {  // a split page: all threads of the block on each
+      const int slot = atomicAdd(&s_nbig, 1);
+      s_big[slot] = i;
+      s_boff[slot] = koff;
+    }
+    __syncthreads();
+    plan_split_pages(job, pp, streams, blks, parts, nj.base, s_nbig, s_big, s_boff);
     return;
   }
+  int np = nn_pages(job);
+  if (y != 0) return;
   // each thread takes a contiguous segment of pages: its loads are
   // independent (one round trip per pass, not one per 1024 pages), one block
   // scan of the segment sums, then the offsets are written in a second pass

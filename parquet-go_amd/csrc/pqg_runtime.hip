@@ -68,8 +68,10 @@ __global__ void k_level_long(PageDev* pages, const int* ctr, const LongLev* long
 __global__ void k_hybrid_walk(const PageDev* pages, const int* list, const int* total, HStream* streams,
                               RunEnt* runs, BlockDesc* blks, LongWalk* longs, int long_cap);
 __global__ void k_walk_long(const int* ctr, const LongWalk* longs, int long_cap, BlockDesc* blks);
+__global__ void k_nn_scan_sums(JobDev* jobs, PageDev* pages, uint8_t* scratch, const HStream* streams, NnSums* sums,
+                               NnJob* njobs, int* ctr, int64_t parts_cap);
 __global__ void k_nn_scan(JobDev* jobs, PageDev* pages, uint8_t* scratch, const HStream* streams, const BlockDesc* blks,
-                          int* ctr, PartRec* parts, int64_t parts_cap);
+                          int* ctr, PartRec* parts, int64_t parts_cap, const NnSums* sums, const NnJob* njobs);
 template <int Mode>
 __global__ void k_values(JobDev* jobs, PageDev* pages, const PartRec* parts, const int* total, int* queue,
                          uint8_t* value_arena, const HStream* streams, const RunEnt* runs, const BlockDesc* blks);
@@ -79,7 +81,7 @@ __global__ void k_dict_plan(JobDev* jobs, PageDev* pages, const PartRec* parts, 
 __global__ void k_dict4(PageDev* pages, const int* total, int* queue, const VRec* recs, int big);
 __global__ void k_dict4_big(PageDev* pages, const int* total, int* queue, const VRec* recs);
 constexpr int kBigDictThreads = 512;
-__global__ void k_finalize(JobDev* jobs, int n_jobs, PageDev* pages);
+__global__ void k_finalize(JobDev* jobs, int n_jobs, const PageDev* pages);
 __global__ void k_str_dict(JobDev* jobs, PageDev* pages, int64_t* doffs_arena);
 __global__ void k_str_count(JobDev* jobs, PageDev* pages, PartRec* parts, const int* total, int* queue,
                             int64_t* offs_arena, const HStream* streams, const RunEnt* runs, const BlockDesc* blks);
@@ -203,6 +205,10 @@ struct pqg_ctx {
   DevBuf parts, lev_long, lev_pieces, walk_long;  // big pages: values-stage parts, long level / value-stream runs
   int64_t parts_cap = 0, lev_long_cap = 0, lev_piece_cap = 0, walk_long_cap = 0;
   int64_t total_tiles = 0;
+  DevBuf nn_sums, nn_jobs;  // k_nn_scan: block sums [job][block], per-job records
+  // grid.y of the per-chunk bookkeeping kernels (pqg_common.h): blocks of kChunkBlock
+  // tiles / pages of the batch's largest chunk, the page blocks capped at kChunkBlocks
+  int tile_blocks = 1, page_blocks = 1;
   JobDev* h_jobs = nullptr;  // pinned
   int h_jobs_cap = 0;
   std::vector<pqg_chunk_job> cur;       // jobs of the in-flight batch
@@ -319,7 +325,7 @@ void pqg_ctx_destroy(pqg_ctx* c) {
                     &c->ok2slot, &c->order, &c->asm_seg, &c->offs_arena, &c->doffs_arena, &c->page_stage,
                     &c->blk_src, &c->blk_dst, &c->blk_meta, &c->tile_job, &c->sn_subs, &c->sn_segpage, &c->sn_F,
                     &c->blk_subs, &c->blk_segpage, &c->blk_F, &c->vrecs, &c->parts, &c->lev_long, &c->lev_pieces,
-                    &c->walk_long})
+                    &c->walk_long, &c->nn_sums, &c->nn_jobs})
     b->release();
   if (c->h_jobs) hipHostFree(c->h_jobs);
   hipStreamDestroy(c->stream);
@@ -483,6 +489,15 @@ static int plan_batch(pqg_ctx* c) {
       c->doffs_arena.grow(sizeof(int64_t) * (size_t)doffs_total + 64))
     return PQG_ERR_HIP;
   c->total_tiles = tile_total;
+  int64_t max_tiles = 0, max_pages = 0;
+  for (int i = 0; i < n; i++) {
+    max_tiles = std::max<int64_t>(max_tiles, c->plan[(size_t)i].n_tiles);
+    max_pages = std::max<int64_t>(max_pages, c->plan[(size_t)i].page_cap);
+  }
+  c->tile_blocks = (int)std::max<int64_t>(1, (max_tiles + kChunkBlock - 1) / kChunkBlock);
+  c->page_blocks = (int)std::min<int64_t>(kChunkBlocks, std::max<int64_t>(1, (max_pages + kChunkBlock - 1) / kChunkBlock));
+  if (c->nn_sums.grow(sizeof(NnSums) * (size_t)n * (size_t)c->page_blocks) || c->nn_jobs.grow(sizeof(NnJob) * (size_t)n))
+    return PQG_ERR_HIP;
   return hip_ok(hipMemcpyAsync(c->jobs.p, c->h_jobs, sizeof(JobDev) * (size_t)n, hipMemcpyHostToDevice, c->stream));
 }
 
@@ -544,23 +559,24 @@ static int launch_pipeline(pqg_ctx* c) {
     int64_t* cpos = (int64_t*)c->cand_pos.p;
     int* clist = (int*)c->cand_list.p;
     const int region = (int)((nt + kQShards - 1) / kQShards) * kCandPerTile;  // one list region per head
-    hipLaunchKernelGGL(k_tile_jobs, dim3(n), dim3(256), 0, s, jobs, (int*)c->tile_job.p);
+    hipLaunchKernelGGL(k_tile_jobs, dim3(n, (unsigned)std::min(c->tile_blocks, 64)), dim3(256), 0, s, jobs, (int*)c->tile_job.p);
     hipLaunchKernelGGL(k_page_cands, dim3((unsigned)nt), dim3(256), 0, s, jobs, (const int*)c->tile_job.p, tcount, tokc,
                        cpos, clist, Q(7),
                        region);
     hipLaunchKernelGGL(k_cand_parse, dim3((unsigned)std::min<int64_t>((nt * kCandPerTile + 255) / 256, c->num_cus * 4)),
                        dim3(256), 0, s, jobs, (const int*)c->tile_job.p, clist, Q(7), region, tokc, cpos, cands);
   }
-  hipLaunchKernelGGL(k_tile_scan, dim3(n), dim3(1024), 0, s, jobs, tcount, tokc, toff, tokoff);
+  const dim3 tile_grid(n, (unsigned)c->tile_blocks), page_grid(n, (unsigned)c->page_blocks);
+  hipLaunchKernelGGL(k_tile_scan, tile_grid, dim3(1024), 0, s, jobs, tcount, tokc, toff, tokoff);
   if (nt > 0)
     hipLaunchKernelGGL(k_cand_link, dim3((unsigned)((nt * kCandPerTile + 255) / 256)), dim3(256), 0, s, jobs,
                        (const int*)c->tile_job.p, nt,
                        tcount, toff, tokoff, cands, (int*)c->succ.p, (int*)c->idx2slot.p, (int*)c->ok2slot.p);
-  hipLaunchKernelGGL(k_page_chain, dim3(n), dim3(1024), 0, s, jobs, pages, cands, (const int*)c->succ.p,
+  hipLaunchKernelGGL(k_page_chain, page_grid, dim3(1024), 0, s, jobs, pages, cands, (const int*)c->succ.p,
                      (const int*)c->idx2slot.p, (const int*)c->ok2slot.p, (int*)c->order.p);
   hipLaunchKernelGGL(k_scan_pages, dim3(n), dim3(64), 0, s, jobs, pages, n, 0, 0);
   if (c->timed) hipEventRecord(c->ev[1], s);
-  hipLaunchKernelGGL(k_page_list, dim3(n), dim3(1024), 0, s, jobs, pages, n, list,
+  hipLaunchKernelGGL(k_page_list, page_grid, dim3(1024), 0, s, jobs, pages, n, list,
                      (int)std::min<int64_t>(c->list_cap, INT32_MAX), ctr, ctr + 8);
   if (c->timed) hipEventRecord(c->ev[2], s);
   bool any_snappy = false, any_gzip = false;
@@ -623,7 +639,12 @@ static int launch_pipeline(pqg_ctx* c) {
   if (c->timed) hipEventRecord(c->ev[5], s);
   if (c->timed) hipEventRecord(c->ev[6], s);
   PartRec* parts = (PartRec*)c->parts.p;
-  hipLaunchKernelGGL(k_nn_scan, dim3(n), dim3(1024), 0, s, jobs, pages, scratch, streams, blks, ctr, parts, c->parts_cap);
+  NnSums* nsums = (NnSums*)c->nn_sums.p;
+  NnJob* njobs = (NnJob*)c->nn_jobs.p;
+  hipLaunchKernelGGL(k_nn_scan_sums, page_grid, dim3(1024), 0, s, jobs, pages, scratch, streams, nsums, njobs, ctr,
+                     c->parts_cap);
+  hipLaunchKernelGGL(k_nn_scan, page_grid, dim3(1024), 0, s, jobs, pages, scratch, streams, blks, ctr, parts, c->parts_cap,
+                     nsums, njobs);
   if (c->timed) hipEventRecord(c->ev[7], s);
   // every values kernel takes the work items (the pages' parts) and keeps the
   // ones whose vmode (set by k_page_levels) is its own
@@ -666,7 +687,7 @@ static int launch_pipeline(pqg_ctx* c) {
                        Q(kQueueStrDba), (uint8_t*)c->value_arena.p, offs);
   }
   if (c->timed) hipEventRecord(c->ev[9], s);
-  hipLaunchKernelGGL(k_finalize, dim3(n), dim3(1024), 0, s, jobs, n, pages);
+  hipLaunchKernelGGL(k_finalize, page_grid, dim3(1024), 0, s, jobs, n, pages);
   if (c->timed) hipEventRecord(c->ev[10], s);
   return hip_ok(hipGetLastError());
 }

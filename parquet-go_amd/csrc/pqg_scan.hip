@@ -27,13 +27,14 @@ struct WinSrc {
 //                     compact-protocol prefix of a PageHeader (field 1 `type`
 //                     i32 with a 1-byte value, then field 2 i32: 15 xx 15);
 //                     each hit is parsed by one lane and classified.
-//   K1b k_tile_scan   per-chunk exclusive scan of the per-tile hit counts.
+//   K1b k_tile_scan   per-chunk exclusive scan of the per-tile hit counts
+//                     (one workgroup per 1024 tiles).
 //   K1c k_cand_link   each candidate finds the candidate at its next-page
 //                     position (its successor).
 //   K1d k_page_chain  pages = the successor chain from position 0.  False
 //                     candidates (payload bytes that happen to parse) are
 //                     never on it.  Pages are written in chain order with the
-//                     slot / scratch prefix sums.
+//                     slot / scratch prefix sums (one workgroup per 1024 pages).
 //   K1e k_scan_pages  the serial walk, run only for chunks the speculative
 //                     path cannot settle (a chain position with no candidate,
 //                     a tile with more than kCandPerTile hits, deep thrift
@@ -273,11 +274,15 @@ __device__ __forceinline__ void parse_candidate(const JobDev& job, int64_t p, Sk
 // cand_total: kQShards counters kQStride ints apart; tile t appends to shard
 // t & 7, whose list region starts at (t & 7) * region (a single list head
 // would take one contended device-scope atomic per tile).
-// tile -> job map (one block per job): the scan kernels look a tile's job up
-// with one load instead of a binary search over the job table.
+// tile -> job map (grid.x: the job, its tiles dealt over grid.y blocks): the
+// scan kernels look a tile's job up with one load instead of a binary search
+// over the job table.
 __global__ void __launch_bounds__(256) k_tile_jobs(const JobDev* jobs, int* tile_job) {
   const JobDev& job = jobs[blockIdx.x];
-  for (int64_t t = threadIdx.x; t < job.n_tiles; t += 256) tile_job[job.tile_base + t] = (int)blockIdx.x;
+  const int nt = job.n_tiles;
+  const int64_t tb = job.tile_base;
+  for (int64_t t = (int64_t)blockIdx.y * 256 + threadIdx.x; t < nt; t += (int64_t)gridDim.y * 256)
+    tile_job[tb + t] = (int)blockIdx.x;
 }
 
 __global__ void __launch_bounds__(256) k_page_cands(JobDev* jobs, const int* tile_job, int* tile_count, int* tile_okc,
@@ -402,45 +407,58 @@ __global__ void __launch_bounds__(256) k_cand_parse(JobDev* jobs, const int* til
 
 // ---- K1b ------------------------------------------------------------------
 // Per-chunk exclusive scans of the tile candidate counts (all, and ok-status).
+// One workgroup per kChunkBlock tiles (grid.x: the job, grid.y: the block; the
+// host sizes grid.y for the chunk with the most tiles).  A block's base is the
+// sum of the counts before it, which it reads itself: one coalesced load per
+// earlier block and lane.  The chunk's last block has then seen every count
+// and writes the job's results.
 __global__ void __launch_bounds__(1024) k_tile_scan(JobDev* jobs, const int* tile_count, const int* tile_okc,
                                                     int* tile_off, int* tile_okoff) {
   __shared__ int64_t part[17];
-  __shared__ int ovf;
   JobDev& job = jobs[blockIdx.x];
   const int tid = threadIdx.x;
   if (job.scan_fallback == 2) return;  // walked before the scan (k_scan_pages prewalk)
-  if (tid == 0) ovf = 0;
-  __syncthreads();
   const int nt = job.n_tiles;
+  const int nblk = (nt + kChunkBlock - 1) / kChunkBlock;
+  const int y = blockIdx.y;
+  if (y >= (nblk > 0 ? nblk : 1)) return;
   const int64_t tb = job.tile_base;
-  // each thread sums a contiguous segment, one block scan, then writes
-  const int seg = (nt + 1023) / 1024;
-  const int s0 = tid * seg, s1 = min(nt, s0 + seg);
-  int64_t sum = 0, oks = 0;
+  int64_t sum = 0, oks = 0;  // this lane's tiles of the earlier blocks
   bool bad = false;
-  for (int t = s0; t < s1; t++) {
-    int c = tile_count[tb + t];
+  for (int q = 0; q < y; q++) {
+    const int c = tile_count[tb + q * kChunkBlock + tid];
     bad |= c > kCandPerTile;
     sum += c;
-    oks += tile_okc[tb + t];
+    oks += tile_okc[tb + q * kChunkBlock + tid];
   }
-  if (bad) ovf = 1;
-  int64_t total, ok_total;
-  int64_t ex = block_excl_scan<1024>(sum, &total, part);
-  int64_t exo = block_excl_scan<1024>(oks, &ok_total, part);
-  for (int t = s0; t < s1; t++) {
-    tile_off[tb + t] = (int)ex;
-    tile_okoff[tb + t] = (int)exo;
-    ex += tile_count[tb + t];
-    exo += tile_okc[tb + t];
+  const int t = y * kChunkBlock + tid;
+  int c = 0, o = 0;
+  if (t < nt) {
+    c = tile_count[tb + t];
+    o = tile_okc[tb + t];
+    bad |= c > kCandPerTile;
   }
+  int64_t pre, opre, total, ok_total;
+  block_excl_scan<1024>(sum, &pre, part);
+  block_excl_scan<1024>(oks, &opre, part);
+  const int64_t ex = block_excl_scan<1024>(c, &total, part);
+  const int64_t exo = block_excl_scan<1024>(o, &ok_total, part);
+  if (t < nt) {
+    tile_off[tb + t] = (int)(pre + ex);
+    tile_okoff[tb + t] = (int)(opre + exo);
+  }
+  if (y != (nblk > 0 ? nblk : 1) - 1) return;
+  const int ovf = __syncthreads_or(bad);
   if (tid == 0) {
+    total += pre;
+    ok_total += opre;
     init_job_results(job);
     job.n_cands = (int32_t)min(total, (int64_t)INT32_MAX);
     job.n_ok = (int32_t)min(ok_total, (int64_t)INT32_MAX);
     job.scan_fallback = (ovf || total > INT32_MAX / 2) ? 1 : 0;
     job.brk = INT32_MAX;
     job.first_dict = INT32_MAX;
+    job.second_dict = INT32_MAX;
   }
 }
 
@@ -510,7 +528,11 @@ __global__ void __launch_bounds__(256) k_cand_link(JobDev* jobs, const int* tile
   succ[tile * kCandPerTile + s] = code;
   if (i == 0 && cd.pos != 0) atomicOr(&job.scan_fallback, 1);
   if (ok && !next_rank) atomicMin(&job.brk, r);
-  if (ok && cd.type == 2) atomicMin(&job.first_dict, r);
+  if (ok && cd.type == 2) {
+    // the two lowest ranks: whichever of the two loses the first minimum goes to the second
+    const int was = atomicMin(&job.first_dict, r);
+    if (was != INT32_MAX) atomicMin(&job.second_dict, was > r ? was : r);
+  }
 }
 
 // ---- K1d ------------------------------------------------------------------
@@ -518,6 +540,12 @@ __global__ void __launch_bounds__(256) k_cand_link(JobDev* jobs, const int* tile
 // candidates of rank 0..brk, plus the failing page the last one links to.
 // Otherwise a serial walk over the links (false ok candidates between pages)
 // or, when a link has no candidate, the serial header walk (K1e).
+// One workgroup per kChunkBlock pages (grid.x: the job, grid.y: the block):
+// every block takes the chain decision again (a few dependent loads), sums
+// num_values / scratch bytes of the pages before its own, and writes its
+// pages' records; the block of the last page writes the job's results.  A
+// walked chain (order[]) and chunks of more than gridDim.y blocks are block
+// 0's alone, in rounds.
 __device__ __forceinline__ bool dict_again(const Cand& c, bool dict_seen) {
   // readPages :221-223: a second DICTIONARY_PAGE fails with "only one
   // dictionary" before its own checks (a header that did not parse fails first)
@@ -529,49 +557,78 @@ __global__ void __launch_bounds__(1024) k_page_chain(JobDev* jobs, PageDev* page
                                                      int* order) {
   __shared__ int64_t part[17];
   __shared__ int s_n, s_mode, s_cut, s_status, s_dict, s_extra, s_nok;
-  const int j = blockIdx.x;
+  const int j = blockIdx.x, y = blockIdx.y;
   JobDev& job = jobs[j];
   const int tid = threadIdx.x;
-  const int64_t lim = job.tcs < job.data_len ? job.tcs : job.data_len;
-  if (job.scan_fallback) return;
-  if (job.tcs <= 0) return;  // the walk reads nothing: no pages
-  if (lim <= 0 || job.n_cands == 0) {
+  // the job's fields in one batch, ahead of the barrier
+  const int64_t tcs = job.tcs, data_len = job.data_len, tile_base = job.tile_base, page_base = job.page_base;
+  const int n_cands = job.n_cands, n_ok = job.n_ok, b = job.brk, d1 = job.first_dict, d2 = job.second_dict,
+            page_cap = job.page_cap;
+  const int64_t lim = tcs < data_len ? tcs : data_len;
+  // one read for the whole block: another block of the job may set it meanwhile
+  if (tid == 0) s_mode = job.scan_fallback;
+  __syncthreads();
+  const bool fb = s_mode != 0;
+  __syncthreads();
+  if (fb) return;
+  if (tcs <= 0) return;  // the walk reads nothing: no pages
+  if (lim <= 0 || n_cands == 0) {
     if (tid == 0) job.scan_fallback = 1;  // a page must start at 0: let the serial walk classify it
     return;
   }
-  const int64_t cb = job.tile_base * kCandPerTile;  // the job's candidate-slot base
+  const int64_t cb = tile_base * kCandPerTile;  // the job's candidate-slot base
   const int* i2s = idx2slot + cb;
   const int* o2s = ok2slot + cb;
-  const int b = job.brk;  // < n_ok when index 0 is ok
-  const int d1 = job.first_dict;
-  const Cand& head = cands[cb + i2s[0]];  // at position 0 (checked by k_cand_link)
+  // (b = brk < n_ok when index 0 is ok)
+  // a chain has at most n_ok + 1 pages: the blocks past them leave at once
+  if ((int64_t)y * kChunkBlock > n_ok) return;
+  // Before the chain decision (a string of dependent loads in lane 0), the
+  // loads that do not wait for it: this lane's page if it is an ok candidate
+  // of the prefix (ranks < n_ok are all linked), and the pages of the blocks
+  // before this one (all ok candidates of the prefix when this block has
+  // pages: none of them is the chain's last page, which alone can fail or be
+  // the second dictionary page).
+  Cand spec;
+  const int slot0 = i2s[0];
+  const int slotb = (n_ok > 0 && b >= 0 && b < n_ok) ? o2s[b] : slot0;  // the prefix's last page
+  {
+    const int k = y * kChunkBlock + tid;
+    spec = cands[cb + (n_ok > 0 ? o2s[k < n_ok ? k : n_ok - 1] : slot0)];
+  }
+  const int codeb = succ[cb + slotb];
+  int64_t slot_carry = 0, scratch_carry = 0;
+  if (y > 0) {
+    int64_t nv = 0, cp = 0;
+    for (int q = tid; q < y * kChunkBlock; q += kChunkBlock) {
+      const Cand& c = cands[cb + o2s[q]];  // q < n_ok
+      const int32_t ty = c.type, cs = c.status, cnv = c.num_values;
+      cp += c.comp;
+      if ((ty == 0 || ty == 3) && cs == kOK) nv += cnv;
+    }
+    block_excl_scan<1024>(nv, &slot_carry, part);
+    block_excl_scan<1024>(cp, &scratch_carry, part);
+  }
+  const Cand& head = cands[cb + slot0];  // at position 0 (checked by k_cand_link)
   if (tid == 0) {
-    s_cut = INT32_MAX;
+    // second dictionary page within ranks (d1, b]
+    s_cut = (head.status == kOK && d2 <= b) ? d2 : INT32_MAX;
     s_mode = 0;
     s_dict = -1;
     s_extra = -1;
     s_nok = 0;
-  }
-  __syncthreads();
-  if (head.status == kOK && d1 < b) {  // second dictionary page within ranks (d1, b]
-    for (int r = d1 + 1 + tid; r <= b; r += 1024)
-      if (cands[cb + o2s[r]].type == 2) atomicMin(&s_cut, r);
-  }
-  __syncthreads();
-  if (tid == 0) {
     int n = 0, mode = 0;  // mode 0: ok prefix (+ extra), 1: walked (order[]), 2: fallback
     if (head.status == kCOMPLEX) {
       mode = 2;
     } else if (head.status != kOK) {  // the first page fails
       n = 1;
-      s_extra = i2s[0];
+      s_extra = slot0;
     } else {
       if (d1 <= b) s_dict = d1;
       if (s_cut != INT32_MAX) {
         n = s_cut + 1;
         s_nok = n;
       } else {
-        const int code = succ[cb + o2s[b]];
+        const int code = codeb;  // succ[cb + o2s[b]]
         s_nok = b + 1;
         n = b + 1;
         if (code == kSuccMissing || code == kSuccComplex) {
@@ -586,14 +643,15 @@ __global__ void __launch_bounds__(1024) k_page_chain(JobDev* jobs, PageDev* page
             if (dict_again(t, d1 <= b)) s_cut = n;
             n++;
           } else {
-            // false ok candidates between pages: walk the links serially
-            int* ord = order + job.page_base;
-            for (int r = 0; r <= b && r < job.page_cap; r++) ord[r] = o2s[r];
+            // false ok candidates between pages: block 0 walks the links serially
+            // (mode 3: the other blocks leave)
+            mode = y == 0 ? 1 : 3;
+            int* ord = order + page_base;
+            for (int r = 0; mode == 1 && r <= b && r < page_cap; r++) ord[r] = o2s[r];
             bool dict_seen = d1 <= b;
             int k = b + 1, cur = code;
-            mode = 1;
-            for (;;) {
-              if (k >= job.page_cap) { mode = 2; break; }
+            while (mode == 1) {
+              if (k >= page_cap) { mode = 2; break; }
               const int sl = i2s[cur];
               const Cand& cd = cands[cb + sl];
               if (cd.status == kCOMPLEX) { mode = 2; break; }
@@ -619,22 +677,27 @@ __global__ void __launch_bounds__(1024) k_page_chain(JobDev* jobs, PageDev* page
     s_status = kOK;
   }
   __syncthreads();
-  if (s_mode == 2) return;
+  if (s_mode >= 2) return;
   const int n = s_n, mode = s_mode, cut = s_cut, nok = s_nok, extra = s_extra;
-  const int nw = n < job.page_cap ? n : job.page_cap;
-  int64_t slot_carry = 0, scratch_carry = 0;
+  const int nw = n < page_cap ? n : page_cap;
+  // this block's rounds: its own, or all of them (block 0 of a walked chain or
+  // of a chunk with more blocks than the grid)
+  const int nblk = (n + kChunkBlock - 1) / kChunkBlock;  // n >= 1
+  const bool spread = mode == 0 && nblk <= (int)gridDim.y;
+  if (spread ? y >= nblk : y != 0) return;
+  const int r0 = spread ? y * kChunkBlock : 0, r1 = spread ? min(n, r0 + kChunkBlock) : n;
   // Rounds of 1024 pages, software-pipelined: the next round's candidate
   // records are loaded before this round's page records are stored (a load
   // issued after the stores would wait for them: vmcnt counts both in order).
   // Loads are unconditional (the page index clamped to n - 1).
   auto fetch = [&](int k, Cand& c) {
     const int kk = k < n ? k : n - 1;
-    const int sl = mode == 1 ? order[job.page_base + kk] : (kk < nok ? o2s[kk] : extra);
+    const int sl = mode == 1 ? order[page_base + kk] : (kk < nok ? o2s[kk] : extra);
     c = cands[cb + sl];
   };
-  Cand cur;
-  if (n > 0) fetch(tid, cur);
-  for (int b0 = 0; b0 < n; b0 += 1024) {
+  Cand cur = spec;  // block 0 of a walked chain starts at page 0 too
+  if (mode == 1 || min(r0 + tid, n - 1) >= nok) fetch(r0 + tid, cur);
+  for (int b0 = r0; b0 < r1; b0 += 1024) {
     const int k = b0 + tid;
     int64_t nv = 0, cp = 0;
     int st = kOK;
@@ -648,7 +711,7 @@ __global__ void __launch_bounds__(1024) k_page_chain(JobDev* jobs, PageDev* page
     const int64_t ex_nv = block_excl_scan<1024>(nv, &tot_nv, part);
     const int64_t ex_cp = block_excl_scan<1024>(cp, &tot_cp, part);
     Cand nxt;
-    if (b0 + 1024 < n) fetch(b0 + 1024 + tid, nxt);
+    if (b0 + 1024 < r1) fetch(b0 + 1024 + tid, nxt);
     if (k < nw) {
       PageDev pg;
       init_page(pg, j, cur.pos, cur.payload);
@@ -664,20 +727,20 @@ __global__ void __launch_bounds__(1024) k_page_chain(JobDev* jobs, PageDev* page
       pg.read_status = st;
       pg.slot_offset = slot_carry + ex_nv;
       if (cp > 0) pg.scratch_offset = scratch_carry + ex_cp;
-      pages[job.page_base + k] = pg;
+      pages[page_base + k] = pg;
     }
     slot_carry += tot_nv;
     scratch_carry += tot_cp;
     cur = nxt;
   }
   __syncthreads();
-  if (tid == 0) {
+  if (tid == 0 && r1 == n) {
     job.num_pages = n;
     job.dict_page = s_dict;
     job.scan_status = s_status;
     job.need_scratch = scratch_carry;
     job.num_slots = slot_carry;
-    if (n > job.page_cap || slot_carry > job.slot_cap || scratch_carry > job.scratch_cap) job.status = kCAPACITY;
+    if (n > page_cap || slot_carry > job.slot_cap || scratch_carry > job.scratch_cap) job.status = kCAPACITY;
   }
 }
 
@@ -979,7 +1042,10 @@ __global__ void __launch_bounds__(64) k_scan_pages(JobDev* jobs, PageDev* pages,
 // ============================================================================
 // K1f: compact list of page indices over all jobs.
 // ============================================================================
-// One 1024-lane block per job: the job's pages in the list (at the offset of
+// One 1024-lane block per kChunkBlock pages of a job (grid.x: the job,
+// grid.y: the block; a block takes the bounds of the pages before its own from
+// their records again, and a job of more than gridDim.y blocks is block 0's,
+// in rounds): the job's pages in the list (at the offset of
 // the pages of the jobs before it), and each data page's region of the value
 // stream's run table / block index — an exclusive scan of a bound from the
 // page's sizes (the same bound reg_stream used to take with two contended
@@ -988,19 +1054,68 @@ __global__ void __launch_bounds__(64) k_scan_pages(JobDev* jobs, PageDev* pages,
 __global__ void __launch_bounds__(1024) k_page_list(JobDev* jobs, PageDev* pages, int n_jobs, int* list, int list_cap,
                                                     int* total, int* queues) {
   __shared__ int64_t part[17];
-  __shared__ int s_off;
-  const int j = blockIdx.x;
+  __shared__ int s_off, s_n;
+  const int j = blockIdx.x, y = blockIdx.y;
+  JobDev& job = jobs[j];
+  // the pages the scan found (no block has pages past them; a job out of
+  // capacity lists none: n below)
+  const int np0 = job.num_pages < job.page_cap ? job.num_pages : job.page_cap;
+  if (y > 0 && (int64_t)y * kChunkBlock >= np0) return;
+  // rounds of 1024 pages, the next round's page fields loaded (unconditionally,
+  // index clamped) before this round's stores: see k_page_chain
+  struct F { int32_t type, usize, csize, nv; int64_t so; };
+  auto fetch = [&](int i, F& f) {
+    const PageDev& pg = pages[job.page_base + (i < np0 ? i : (np0 > 0 ? np0 - 1 : 0))];
+    f.type = pg.page_type;
+    f.usize = pg.usize;
+    f.csize = pg.csize;
+    f.nv = pg.num_values;
+    f.so = pg.scratch_offset;
+  };
+  auto bounds = [](const F& f, int64_t* nr, int64_t* nb) {
+    *nr = *nb = 0;
+    if (f.type == 0 || f.type == 3) {
+      const int64_t B = f.so >= 0 ? (int64_t)(uint32_t)f.usize : (int64_t)(uint32_t)f.csize;
+      *nr = B / 2 + 2;
+      // the lane walker's greedy blocks: n/kHBlock + runs/kHBlockRuns + B/(kHBlockBytes/2) + 3
+      *nb = (int64_t)(uint32_t)f.nv / kHBlock + *nr / kHBlockRuns + B / (kHBlockBytes / 2) + 3;
+    }
+  };
+  // this block's first round and the pages before it, loaded before lane 0's
+  // walk over the job table so that the round trips overlap
+  F cur;
+  fetch(y * kChunkBlock + (int)threadIdx.x, cur);
+  int64_t rc = 0, bc = 0;
+  if (y > 0) {
+    for (int q = threadIdx.x; q < y * kChunkBlock; q += kChunkBlock) {
+      F f;
+      fetch(q, f);
+      int64_t nr, nb;
+      bounds(f, &nr, &nb);
+      rc += nr;
+      bc += nb;
+    }
+    int64_t tot;
+    block_excl_scan<1024>(rc, &tot, part);
+    rc = tot;
+    block_excl_scan<1024>(bc, &tot, part);
+    bc = tot;
+  }
   auto pages_of = [&](int i) {
     int n = jobs[i].num_pages;
     if (n > jobs[i].page_cap) n = jobs[i].page_cap;
     if (jobs[i].status == kCAPACITY) n = 0;
     return n;
   };
+  // the pages of the jobs before this one: one job per lane, not a walk
+  int64_t before = 0, before_tot;
+  for (int i = threadIdx.x; i < j; i += kChunkBlock) before += pages_of(i);
+  block_excl_scan<1024>(before, &before_tot, part);
   if (threadIdx.x == 0) {
-    int off = 0;
-    for (int i = 0; i < j; i++) off += pages_of(i);
+    const int off = (int)before_tot;
     s_off = off;
-    if (j == n_jobs - 1) {
+    s_n = pages_of(j);  // one read for the whole block: the job's last block may set its status meanwhile
+    if (j == n_jobs - 1 && y == 0) {
       const int all = off + pages_of(j);
       *total = all < list_cap ? all : list_cap;
       for (int q = 0; q < 16; q++) queues[q] = 0;  // ctr[8..23]
@@ -1009,36 +1124,20 @@ __global__ void __launch_bounds__(1024) k_page_list(JobDev* jobs, PageDev* pages
   }
   __syncthreads();
   const int off = s_off;
-  JobDev& job = jobs[j];
-  const int n = pages_of(j);
-  int64_t rc = 0, bc = 0;
-  // rounds of 1024 pages, the next round's page fields loaded (unconditionally,
-  // index clamped) before this round's stores: see k_page_chain
-  struct F { int32_t type, usize, csize, nv; int64_t so; };
-  auto fetch = [&](int i, F& f) {
-    const PageDev& pg = pages[job.page_base + (i < n ? i : n - 1)];
-    f.type = pg.page_type;
-    f.usize = pg.usize;
-    f.csize = pg.csize;
-    f.nv = pg.num_values;
-    f.so = pg.scratch_offset;
-  };
-  F cur;
-  if (n > 0) fetch((int)threadIdx.x, cur);
-  for (int b = 0; b < n; b += 1024) {
+  const int n = s_n;  // np0, or 0
+  const int nblk = (n + kChunkBlock - 1) / kChunkBlock;
+  const bool spread = nblk <= (int)gridDim.y;
+  if (spread ? y >= (nblk > 0 ? nblk : 1) : y != 0) return;
+  const int r0 = spread ? y * kChunkBlock : 0, r1 = spread ? min(n, r0 + kChunkBlock) : n;
+  for (int b = r0; b < r1; b += 1024) {
     const int i = b + threadIdx.x;
     int64_t nr = 0, nb = 0;
-    if (i < n && (cur.type == 0 || cur.type == 3)) {
-      const int64_t B = cur.so >= 0 ? (int64_t)(uint32_t)cur.usize : (int64_t)(uint32_t)cur.csize;
-      nr = B / 2 + 2;
-      // the lane walker's greedy blocks: n/kHBlock + runs/kHBlockRuns + B/(kHBlockBytes/2) + 3
-      nb = (int64_t)(uint32_t)cur.nv / kHBlock + nr / kHBlockRuns + B / (kHBlockBytes / 2) + 3;
-    }
+    if (i < n) bounds(cur, &nr, &nb);
     int64_t tr, tb;
     const int64_t er = block_excl_scan<1024>(nr, &tr, part);
     const int64_t eb = block_excl_scan<1024>(nb, &tb, part);
     F nxt;
-    if (b + 1024 < n) fetch(b + 1024 + (int)threadIdx.x, nxt);
+    if (b + 1024 < r1) fetch(b + 1024 + (int)threadIdx.x, nxt);
     if (i < n) {
       if (off + i < list_cap) list[off + i] = (int)(job.page_base + i);
       pages[job.page_base + i].run_off = rc + er;
@@ -1048,9 +1147,14 @@ __global__ void __launch_bounds__(1024) k_page_list(JobDev* jobs, PageDev* pages
     bc += tb;
     cur = nxt;
   }
-  if (threadIdx.x == 0) {
-    job.run_used = rc;
-    job.blk_used = bc;
+  if (threadIdx.x == 0 && r1 == n) {
+    job.fin_read = job.fin_dec = INT32_MAX;  // k_finalize
+    job.fin_done = job.nn_done = 0;
+    job.nn_acc = job.parts_acc = 0;  // k_nn_scan_sums
+    // (a maximum over the 0 of init_job_results: block 0 is the last block too
+    // when it reads the status set below by the real one, and then has rc = 0)
+    atomicMax((unsigned long long*)&job.run_used, (unsigned long long)rc);
+    atomicMax((unsigned long long*)&job.blk_used, (unsigned long long)bc);
     if (rc > job.run_cap || bc > job.blk_cap) job.status = kCAPACITY;  // the host grows the run arenas
   }
 }

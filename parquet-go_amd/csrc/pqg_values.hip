@@ -946,12 +946,16 @@ template __global__ void k_values<3>(JobDev*, PageDev*, const PartRec*, const in
 
 // ============================================================================
 // K5: chunk status in reference order (readPages errors first, then
-// readPageData errors) — one 256-lane block per job, min-reductions over pages.
+// readPageData errors).  The first page with a read error and the first data
+// page with a decode error: a minimum over the job's pages (grid.x: the job,
+// its pages dealt over grid.y blocks) into two words of the job that
+// k_page_list reset; the job's block that adds its minima last composes the
+// status.
 // ============================================================================
-__global__ void __launch_bounds__(1024) k_finalize(JobDev* jobs, int n_jobs, PageDev* pages) {
+__global__ void __launch_bounds__(1024) k_finalize(JobDev* jobs, int n_jobs, const PageDev* pages) {
   __shared__ int s_read, s_dec;
   JobDev& job = jobs[blockIdx.x];
-  if (job.status == kCAPACITY) return;
+  if (job.status == kCAPACITY) return;  // (set before this kernel: the status is written below after every block has read it)
   const int np = job.num_pages < job.page_cap ? job.num_pages : job.page_cap;
   if (threadIdx.x == 0) {
     s_read = INT32_MAX;
@@ -961,7 +965,7 @@ __global__ void __launch_bounds__(1024) k_finalize(JobDev* jobs, int n_jobs, Pag
   const PageDev* pg = pages + job.page_base;
   int r = INT32_MAX, d = INT32_MAX;
 #pragma unroll 8
-  for (int i = threadIdx.x; i < np; i += 1024) {
+  for (int i = blockIdx.y * 1024 + threadIdx.x; i < np; i += gridDim.y * 1024) {
     if (pg[i].read_status != kOK && i < r) r = i;
     if ((pg[i].page_type == 0 || pg[i].page_type == 3) && pg[i].decode_status != kOK && i < d) d = i;
   }
@@ -969,14 +973,20 @@ __global__ void __launch_bounds__(1024) k_finalize(JobDev* jobs, int n_jobs, Pag
   if (d != INT32_MAX) atomicMin(&s_dec, d);
   __syncthreads();
   if (threadIdx.x != 0) return;
+  if (s_read != INT32_MAX) atomicMin(&job.fin_read, s_read);
+  if (s_dec != INT32_MAX) atomicMin(&job.fin_dec, s_dec);
+  __threadfence();
+  if (atomicAdd(&job.fin_done, 1) != (int)gridDim.y - 1) return;
+  __threadfence();
+  const int f_read = atomicMin(&job.fin_read, INT32_MAX), f_dec = atomicMin(&job.fin_dec, INT32_MAX);  // reads
   int status = kOK, ep = -1;
-  if (s_read != INT32_MAX) {
-    ep = s_read;
+  if (f_read != INT32_MAX) {
+    ep = f_read;
     status = pg[ep].read_status;
   }
   job.n_out_pages = ep >= 0 ? ep + 1 : np;
-  if (status == kOK && s_dec != INT32_MAX) {
-    ep = s_dec;
+  if (status == kOK && f_dec != INT32_MAX) {
+    ep = f_dec;
     status = pg[ep].decode_status;
   }
   job.status = status;
