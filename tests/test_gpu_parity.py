@@ -5,6 +5,7 @@ full-size configs are checked by bench.py's verify pass against the
 generator's own arrays (`verified_bit_exact`), and cases larger than the
 kernels' LDS windows (long runs, >= 1 MiB snappy pages, long DBA values) by
 test_levels.py, test_snappy_split.py and test_delta_strings.py.
+GZIP pages of DEFLATE streams no encoder writes: test_inflate_layouts.py.
 """
 import json
 import os

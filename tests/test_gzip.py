@@ -6,7 +6,8 @@ The reference's own tests only round-trip gzip (compress_test.go:11-32), so the
 oracle is checked here against pyarrow-written GZIP files (an independent
 writer and reader) and against hand-built pages: two concatenated members
 (Go's default multistream mode reads both), a corrupt member, trailing
-garbage, a truncated member."""
+garbage, a truncated member.
+DEFLATE streams that zlib's encoder never emits: test_inflate_layouts.py."""
 import gzip
 import io
 import zlib
