@@ -4,19 +4,27 @@
 // The page's def stream (<= kL1MaxN bytes) is staged in LDS with one round of
 // loads and decoded with no per-batch loop:
 //   1. backward exit table: lane l owns stream positions [l S, l S + S) (S =
-//      ceil(n / 64) <= 64) and walks them from the last to the first, parsing
-//      a run header at every position (hybridDecoder.readRunHeader,
-//      hybrid_decoder.go:143-166; RLE value / bit-packed extent :116-141).
-//      Position p's exit — the first header position at or past the segment's
-//      end on the chain from p — is the successor's exit when the successor is
-//      inside the segment (already known: headers are >= 2 bytes apart), else
-//      the successor itself.  One byte per position (offset past the
-//      segment's end, "far", or "bad": an error or a 5-byte header on the way);
+//      ceil(n / 64) <= 64, a multiple of 4) and walks them from the last to
+//      the first, parsing a run header at every position
+//      (hybridDecoder.readRunHeader, hybrid_decoder.go:143-166; RLE value /
+//      bit-packed extent :116-141).  Position p's exit — the first header
+//      position at or past the segment's end on the chain from p — is the
+//      successor's exit when the successor is inside the segment (already
+//      known: headers are >= 2 bytes apart), else the successor itself.  One
+//      byte per position (offset past the segment's end, "far", or "bad": an
+//      error on the way).  Four positions a step, one per byte lane of a
+//      dword (l1_quad, pqg_lev1_parse.h): headers of one and two bytes are
+//      settled there, every other one is "far"; the positions next to the
+//      stream's end, where the checks against it matter, are parsed one at a
+//      time with the byte-wise l1_hdr;
 //   2. link: the true chain's entry into every segment, 64 dependent table
-//      reads (entry(l + 1) = exit(entry(l)) from position 0);
+//      reads (entry(l + 1) = exit(entry(l)) from position 0); a "far" exit is
+//      walked header by header with l1_hdr;
 //   3. each lane walks its segment's part of the chain twice: the value count
 //      (a saturating wave scan gives every lane its first value), then the
-//      bits, OR-ed into an LDS bitmap of the page's values;
+//      bits, appended word by word to an LDS bitmap of the page's values in
+//      one loop over the lane's words (a step places up to 32 values of the
+//      current run and moves on to the next run when that one is used up);
 //   4. the wave expands the bitmap 16 values per lane (nibble x 0x00204081)
 //      into aligned 16-byte stores of level bytes and counts notNull.
 // No global store happens before every check has passed; a page this path
@@ -26,51 +34,19 @@
 // reference's error (hybridDecoder.next, hybrid_decoder.go:82-114).
 #pragma once
 #include "pqg_levdec.h"
+#include "pqg_lev1_parse.h"
 
 namespace pqg {
 
 constexpr int kL1MaxN = 4096;               // stream bytes
 constexpr int kL1MaxCount = 32768 - 16;     // values (+ <= 15 alignment bits: a 4 KiB bitmap)
 constexpr int kL1Win = kL1MaxN + 64;        // window: 15 alignment bytes, the stream, zeros for reads past n
-constexpr uint32_t kL1Far = 254, kL1Bad = 255;
 
 struct Lev1Shared {
   uint8_t win[kL1Win];
   uint32_t tab[kL1MaxN / 4 + 2];  // exit codes (one byte per position), then the value bitmap
 };
 
-struct L1Hdr {
-  uint32_t nx;   // position of the next header
-  uint32_t cnt;  // values of the run
-  uint32_t pay;  // bit-packed: payload position; RLE: the value
-  bool bp, bad;
-};
-
-// The run header at stream position q (win[mis + q] = byte q, zeros past n):
-// readUVariant32 (helpers.go:149-165) for headers of <= 4 bytes; 5+ byte
-// headers, EOF inside the header or the RLE value, empty runs and RLE values
-// >= 2 are `bad` (the exact decoder settles them).
-// lo / hi: stream bytes q..q+3 / q+4..q+7.
-__device__ __forceinline__ L1Hdr l1_hdr(uint32_t lo, uint32_t hi, uint32_t q, uint32_t n) {
-  // branch-free (every position of a segment is parsed: divergent bit-packed
-  // / RLE branches would run both sides)
-  const uint32_t cont = ~lo & 0x80808080u;
-  const uint32_t hl = (cont ? (uint32_t)__builtin_ctz(cont) >> 3 : 4u) + 1;  // 5: no terminating byte in four
-  const uint32_t hf = (lo & 0x7f) | ((lo >> 1) & 0x3f80) | ((lo >> 2) & 0x1fc000) | ((lo >> 3) & 0xfe00000);
-  const uint32_t h = __builtin_amdgcn_ubfe(hf, 0, 7 * hl);  // hl 5: garbage, and bad below
-  const uint32_t g = h >> 1;
-  const bool bp = (h & 1) != 0;
-  const uint32_t vb = (uint32_t)((((uint64_t)hi << 32) | lo) >> (8 * hl)) & 0xff;  // the byte after the header
-  const uint32_t ve = q + hl;
-  L1Hdr r;
-  r.bp = bp;
-  // readRLERunValue: the value byte must be there and < 2^w (:116-131)
-  r.bad = (hl > 4) | (ve > n) | (g == 0) | (!bp & ((ve >= n) | (vb > 1)));  // bitwise: no branches
-  r.cnt = bp ? g * 8 : g;  // g < 2^27
-  r.pay = bp ? ve : vb;
-  r.nx = ve + (bp ? g : 1u);
-  return r;
-}
 __device__ __forceinline__ L1Hdr l1_parse(const PQG_L uint8_t* win, uint32_t mis, uint32_t q, uint32_t n) {
   const uint32_t wo = mis + q;
   const PQG_L uint32_t* d = (const PQG_L uint32_t*)(win + (wo & ~3u));
@@ -105,26 +81,6 @@ __device__ __forceinline__ L1Run l1_run(const PQG_L uint8_t* win, uint32_t mis, 
 __device__ __forceinline__ uint32_t l1_code(const L1Hdr& h, uint32_t e) {
   const uint32_t d = h.nx - e;
   return h.bad ? kL1Bad : (d < kL1Far ? d : kL1Far);
-}
-
-// OR the bits of values [s, s + len) of one run into the bitmap: bit-packed
-// runs take window bits from `sbit`, RLE runs of value 1 ones.
-__device__ __forceinline__ void l1_or_run(PQG_L uint32_t* bm, const PQG_L uint32_t* W, uint32_t s, uint32_t len,
-                                          bool bp, uint32_t sbit) {
-  const uint32_t e = s + len;
-  for (uint32_t k = s >> 5; 32 * k < e; k++) {
-    const uint32_t lo = s > 32 * k ? s : 32 * k;
-    const uint32_t hi = e < 32 * k + 32 ? e : 32 * k + 32;
-    const uint32_t cnt = hi - lo;
-    const uint32_t m = cnt >= 32 ? 0xffffffffu : ((1u << cnt) - 1);
-    uint32_t v = m;
-    if (bp) {
-      const uint32_t sb = sbit + (lo - s);
-      v = __builtin_amdgcn_alignbit(W[(sb >> 5) + 1], W[sb >> 5], sb & 31) & m;
-    }
-    v <<= (lo - 32 * k);
-    if (v) __hip_atomic_fetch_or(bm + k, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
-  }
 }
 
 // Decode `count` 1-bit levels of stream [p, p + n) into out[0, count) and
@@ -162,46 +118,53 @@ __device__ __forceinline__ bool lev1_page(gcu8 p, uint32_t n, uint32_t count, gu
   const uint32_t S = (((n + 63) >> 6) + 3) & ~3u;  // a multiple of 4, <= 64
   const uint32_t a = (uint32_t)lane * S;
   const uint32_t e = a + S < n ? a + S : n;
-  // the top (e - a) % 4 positions one at a time, then groups of four: the
-  // four headers from one 16-byte read, their successors' codes read together
-  // (a header's successor is >= 2 positions on: the group's two upper codes
-  // are forwarded to its two lower positions in registers)
+  // the top (e - a) % 4 positions one at a time with the exact parse, and
+  // with them the group that holds positions >= n - 3 (the checks against the
+  // stream's end and reads of the padding concern those alone); then groups
+  // of four with the bytewise parse.
   int q = (int)e - 1;
-  for (int r = (int)((e > a ? e - a : 0u) & 3); r > 0; r--, q--) {
+  const uint32_t len = e > a ? e - a : 0u;
+  uint32_t top = len & 3;
+  if (e - top + 3 > n) top += 4;  // a position >= n - 3 below them
+  top = top < len ? top : len;
+  for (int r = (int)top; r > 0; r--, q--) {
     const L1Hdr h = l1_parse(win, mis, (uint32_t)q, n);
     uint32_t code = l1_code(h, e);
     if (!h.bad && h.nx < e) code = T[h.nx];
     T[q] = (uint8_t)code;
   }
+  // Four positions from one 12-byte read: l1_quad settles headers of one and
+  // two bytes and calls the rest "far", the code that already sends the link
+  // (2.) down the chain with the exact parse.  Calling a position far is
+  // therefore always correct (a far position passes its code to every
+  // position that leads to it: the link then walks that segment header by
+  // header) and costs time only on the true chain.  The codes are selected
+  // bytewise as well; the successors' codes are read together (a header's
+  // successor is >= 2 positions on: the group's two upper codes are forwarded
+  // to its two lower positions in registers).
   for (; q >= (int)a + 3; q -= 4) {
     const uint32_t q0 = (uint32_t)q - 3;  // positions q0 .. q0 + 3
     const uint32_t wo = mis + q0;
     const PQG_L uint32_t* d = (const PQG_L uint32_t*)(win + (wo & ~3u));
-    const uint32_t d0 = d[0], d1 = d[1], d2 = d[2], d3 = d[3];
-    const uint32_t o = wo & 3;  // byte of position q0 in d0
-    L1Hdr h[4];
+    const uint32_t d0 = d[0], d1 = d[1], d2 = d[2];
+    const uint32_t sft = (wo & 3) * 8;
+    const uint32_t b0 = __builtin_amdgcn_alignbit(d1, d0, sft), b4 = __builtin_amdgcn_alignbit(d2, d1, sft);
+    const L1Quad h = l1_quad(b0, __builtin_amdgcn_alignbit(b4, b0, 8), __builtin_amdgcn_alignbit(b4, b0, 16));
+    const L1Codes cd = l1_quad_codes(h, e - q0);
+    const uint32_t in7 = cd.in, code = cd.code;
+    const uint32_t inm = in7 | (in7 - (in7 >> 7));
+    uint32_t nx[4], t[4];
 #pragma unroll
     for (int j = 0; j < 4; j++) {
-      const uint32_t oj = o + j;  // 0..6
-      const uint32_t sft = (oj & 3) * 8;
-      const bool up = oj >= 4;
-      const uint32_t x0 = up ? d1 : d0, x1 = up ? d2 : d1, x2 = up ? d3 : d2;
-      h[j] = l1_hdr(__builtin_amdgcn_alignbit(x1, x0, sft), __builtin_amdgcn_alignbit(x2, x1, sft), q0 + j, n);
-    }
-    uint32_t t[4], c[4];
-    bool in[4];
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      in[j] = !h[j].bad & (h[j].nx < e);
-      t[j] = T[in[j] ? h[j].nx : q0 + 3];  // unconditional (clamped) read
-      c[j] = l1_code(h[j], e);
+      nx[j] = q0 + j + ((h.len >> (8 * j)) & 0xff);
+      t[j] = T[(in7 >> (8 * j + 7)) & 1 ? nx[j] : q0 + 3];  // unconditional (clamped) read
     }
     // successors inside the group come from registers (q0 + 2 / q0 + 3: written below)
-    const uint32_t c3 = in[3] ? t[3] : c[3];
-    const uint32_t c2 = in[2] ? t[2] : c[2];  // successor >= q0 + 4
-    const uint32_t c1 = in[1] ? (h[1].nx == q0 + 3 ? c3 : t[1]) : c[1];
-    const uint32_t c0 = in[0] ? (h[0].nx == q0 + 3 ? c3 : h[0].nx == q0 + 2 ? c2 : t[0]) : c[0];
-    *(PQG_L uint32_t*)(T + q0) = c0 | c1 << 8 | c2 << 16 | c3 << 24;  // q0 = a + 4k: aligned
+    const uint32_t up = (code & ~inm) | ((t[2] << 16 | t[3] << 24) & inm);  // successor >= q0 + 4
+    const uint32_t c3 = up >> 24, c2 = (up >> 16) & 0xff;
+    const uint32_t t1 = nx[1] == q0 + 3 ? c3 : t[1];
+    const uint32_t t0 = nx[0] == q0 + 3 ? c3 : nx[0] == q0 + 2 ? c2 : t[0];
+    *(PQG_L uint32_t*)(T + q0) = up | ((t0 | t1 << 8) & inm);  // q0 = a + 4k: aligned
   }
   __builtin_amdgcn_wave_barrier();
   PQG_T(t2);
@@ -287,47 +250,56 @@ __device__ __forceinline__ bool lev1_page(gcu8 p, uint32_t n, uint32_t count, gu
   // the next run's header is read while the current one's bits are placed
   uint32_t rq = 0;
   L1Run r{};
-  if (m) {
+  bool have = m != 0;  // r: a run to place
+  if (have) {
     rq = a + (uint32_t)__builtin_ctzll(m);
     m &= m - 1;
     r = l1_run(win, mis, rq);
   }
-  bool more = c < count && cm != 0;
-  while (more) {
-    const L1Run cur = r;
-    const uint32_t cq = rq;
-    const bool next = m != 0;
-    if (next) {
-      rq = a + (uint32_t)__builtin_ctzll(m);
-      m &= m - 1;
-      r = l1_run(win, mis, rq);
-    }
-    const uint32_t cnt = cur.bp ? cur.g * 8 : cur.g;
-    uint32_t take = cnt < count - c ? cnt : count - c;
-    const uint32_t pay = cq + cur.hl;  // bit-packed payload
-    // a short read: the last needed group must start inside the stream (Q5)
-    if (cur.bp && pay + ((take + 7) >> 3) - 1 >= n) { fail = true; break; }
-    c += take;
-    const uint32_t pat = cur.vb ? 0xffffffffu : 0u;  // RLE
-    const bool bp = cur.bp;
-    uint32_t sb = bp ? (mis + pay) * 8 : 0u;
-    while (take) {
-      const uint32_t nb = take < 32 ? take : 32;
-      const uint32_t src = __builtin_amdgcn_alignbit(W[(sb >> 5) + 1], W[sb >> 5], sb & 31);
-      const uint32_t bits = (bp ? src : pat) & (nb >= 32 ? 0xffffffffu : ((1u << nb) - 1));
-      acc |= (uint64_t)bits << fill;
-      fill += nb;
-      take -= nb;
-      sb += nb;
-      if (fill >= 32) {
-        flush((uint32_t)acc);
-        acc >>= 32;
-        fill -= 32;
+  // One loop, a step of which places up to 32 values of the lane's current
+  // run; a lane whose run is used up first moves on to its next one in the
+  // same step.  The wave takes as many steps as its busiest lane has words,
+  // not the longest run of every round of runs.
+  uint32_t take = 0, sb = 0, pat = 0;
+  bool bp = false;
+  while (have | (take != 0)) {
+    if (take == 0) {
+      const uint32_t cnt = r.bp ? r.g * 8 : r.g;
+      take = cnt < count - c ? cnt : count - c;  // >= 1: c < count, and no run on the chain is empty
+      const uint32_t pay = rq + r.hl;  // bit-packed payload
+      // a short read: the last needed group must start inside the stream (Q5)
+      if (r.bp && pay + ((take + 7) >> 3) - 1 >= n) { fail = true; break; }
+      c += take;
+      have = m != 0 && c < count;
+      pat = r.vb ? 0xffffffffu : 0u;  // RLE
+      bp = r.bp;
+      sb = bp ? (mis + pay) * 8 : 0u;
+      // the next run's header, after the last use of this one's: its read is
+      // waited for a step later
+      if (have) {
+        rq = a + (uint32_t)__builtin_ctzll(m);
+        m &= m - 1;
+        r = l1_run(win, mis, rq);
       }
     }
-    more = next && c < count;
+    const uint32_t nb = take < 32 ? take : 32;
+    const uint32_t src = __builtin_amdgcn_alignbit(W[(sb >> 5) + 1], W[sb >> 5], sb & 31);
+    const uint32_t bits = (bp ? src : pat) & (nb >= 32 ? 0xffffffffu : ((1u << nb) - 1));
+    acc |= (uint64_t)bits << fill;
+    fill += nb;
+    take -= nb;
+    sb += nb;
+    if (fill >= 32) {
+      flush((uint32_t)acc);
+      acc >>= 32;
+      fill -= 32;
+    }
   }
-  if (fill) {
+  // the last, partly filled word, of a lane whose first value lies inside the
+  // page: 32 k < pre + c <= pre + count, so k < nw.  (A lane whose first value
+  // is at or past `count` placed nothing, and with B saturating at 2^24 its
+  // word index lies outside the zeroed words, and can lie outside the table.)
+  if (fill && B < count) {
     __hip_atomic_fetch_or(bm + k, (uint32_t)acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
     nn += __builtin_popcount((uint32_t)acc);
   }
