@@ -374,8 +374,56 @@ typedef struct pqg_list_args {
  * PQG_ERR_INVALID_ARG when elements exceed int32 offsets. */
 int pqg_assemble_list(pqg_ctx* ctx, pqg_list_args* args);
 
+/* ---- K8 nested export: Arrow layout of every list depth on a leaf's path ----
+ * The general form of the list export, for a leaf under depth = max_rep lists
+ * (0..PQG_MAX_LIST_DEPTH) with a fixed-width or a byte-array value.  It
+ * replaces the recursion of Column.getData / getNextData (schema.go:171-264)
+ * over ColumnStore.get (data_store.go:158-203).  Depth k (1..depth) has two
+ * definition-level thresholds, level[k-1].elem_def (the k-th REPEATED node of
+ * the path: the list has an element) and level[k-1].list_def (the list is not
+ * null).  With elem_def[0] = 0, for slot i:
+ *   entry_k(i) = rep[i] <= k-1 && def[i] >= elem_def[k-1]   a depth-k list starts
+ *   valid_k(i) = def[i] >= list_def[k]                      its validity bit
+ *   elem_k(i)  = rep[i] <= k   && def[i] >= elem_def[k]     (= entry_{k+1})
+ *   leaf(i)    = elem_depth(i);  leaf_valid(i) = def[i] == max_def
+ *   offsets_k[rank entry_k(i)] = #elem_k before i;  offsets_k[#entry_k] = #elem_k
+ * valid_k's bit goes at rank entry_k(i), the leaf's at rank leaf(i).  A
+ * fixed-width leaf value is dense[rank leaf_valid], zeros for a null; a
+ * byte-array leaf gets leaf_offsets[e] = value_offsets[#valid before e] and
+ * leaf_offsets[num_leaf] = value_offsets[num_valid], so a null is an empty
+ * string over the decoded chars as they are.  rep_levels NULL: every rep is 0;
+ * def_levels NULL (only with max_def == 0): everything is present.  depth 1 is
+ * pqg_assemble_list; depth 0 is flat validity and spaced values / offsets.
+ * Required: elem_def[k-1] <= list_def[k] <= elem_def[k] <= max_def with
+ * elem_def strictly increasing (PQG_ERR_INVALID_ARG); depth outside
+ * 0..PQG_MAX_LIST_DEPTH is PQG_ERR_UNSUPPORTED; leaf_values needs values and
+ * value_width > 0, leaf_offsets needs value_offsets.  More elements at any
+ * depth than int32 offsets hold is PQG_ERR_INVALID_ARG.  No output is written
+ * when the call fails.  Bitmaps are zeroed by the call and written as whole
+ * dwords. */
+#define PQG_MAX_LIST_DEPTH 4
+typedef struct pqg_nested_level {
+  int32_t list_def, elem_def;
+  uint8_t* validity;     /* out, DEVICE, 4*ceil(num_slots/32) bytes, or NULL */
+  int32_t* offsets;      /* out, DEVICE, entries+1 (cap num_slots+1), or NULL */
+  int64_t num_entries;   /* out */
+  int64_t null_count;    /* out */
+} pqg_nested_level;
+typedef struct pqg_nested_args {
+  const uint8_t *def_levels, *rep_levels, *values;
+  const int64_t* value_offsets;     /* byte-array leaf: the chunk result's offsets, else NULL */
+  int64_t num_slots;
+  int32_t max_def, depth, value_width, reserved;
+  pqg_nested_level level[PQG_MAX_LIST_DEPTH];
+  uint8_t* leaf_validity; /* out: 4*ceil(num_slots/32) bytes */
+  uint8_t* leaf_values;   /* out: num_leaf x value_width (cap num_slots) */
+  int64_t* leaf_offsets;  /* out: num_leaf+1 (cap num_slots+1); any of the three may be NULL */
+  int64_t num_rows, num_leaf, num_valid;                                /* out */
+} pqg_nested_args;
+int pqg_assemble_nested(pqg_ctx* ctx, pqg_nested_args* args);
+
 /* Device time (ms) of the K8 kernels of the last pqg_assemble /
- * pqg_assemble_list call: HIP events on the ctx stream around its kernel
+ * pqg_assemble_list / pqg_assemble_nested call: HIP events on the ctx stream around its kernel
  * launches (the count read-back and host syncs excluded). */
 int pqg_last_assemble_ms(pqg_ctx* ctx, float* ms);
 

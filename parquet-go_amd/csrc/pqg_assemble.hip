@@ -358,6 +358,305 @@ int list_write_launch(hipStream_t s, const pqg_list_args* a, int64_t* seg_scratc
 }
 
 // ---------------------------------------------------------------------------
+// Nested export (pqg_assemble_nested): the Arrow layout of every list depth on
+// a leaf's path, K = max_rep lists deep (0..PQG_MAX_LIST_DEPTH).  It replaces
+// the nested cursor walk of Column.getData / getNextData (schema.go:171-264)
+// over ColumnStore.get (data_store.go:158-203).  With elem_def[0] = 0, a slot
+// (rep, def) is
+//   e_k   = rep <= k && def >= elem_def[k]     k = 0..K
+// an element of a depth-k list (e_0: a row start) and, being one, the entry of
+// a depth-(k+1) list whose validity bit is def >= list_def[k+1]; e_K is a leaf
+// slot, valid when def == max_def.  One predicate per depth therefore gives
+// both ranks a depth needs: offsets_k[rank e_{k-1}] = rank e_k.  Per segment the
+// counters are rows, e_1..e_K, valid leaves (the K + 2 ranks) and the null
+// lists of each depth (totals only).  Same three launches as the list export;
+// the depth is a template parameter, so the K = 1 instance carries no other
+// depth's masks or bases.  Both passes read 4-byte-aligned level streams a
+// dword per lane, 256 slots a round (the write pass hands the bytes round
+// with ds_bpermute so that each ballot is in slot order), and fall back to a
+// byte per lane for unaligned streams and the last partial group.
+// ---------------------------------------------------------------------------
+struct NestThr {
+  int list_def[PQG_MAX_LIST_DEPTH], elem_def[PQG_MAX_LIST_DEPTH];  // [k-1] for depth k
+};
+struct NestOut {
+  uint32_t* validity[PQG_MAX_LIST_DEPTH];
+  int32_t* offsets[PQG_MAX_LIST_DEPTH];
+};
+
+template <int K>
+struct NestPred {
+  bool e[K + 1];  // e[k]: element of a depth-k list (e[0]: row start)
+  bool valid;     // def == max_def: consumes the next dense value
+  int d;          // def level, -1 outside the segment
+};
+// from the slot's two levels (outside the segment: d = -1, r = 255)
+template <int K>
+__device__ __forceinline__ NestPred<K> nest_pred_of(int d, int r, int max_def, const NestThr& th) {
+  NestPred<K> p;
+  p.d = d;
+  p.e[0] = r == 0;
+#pragma unroll
+  for (int k = 1; k <= K; k++) p.e[k] = r <= k && d >= th.elem_def[k - 1];
+  p.valid = d == max_def;
+  return p;
+}
+template <int K>
+__device__ __forceinline__ NestPred<K> nest_pred(const PQG_G uint8_t* def, const PQG_G uint8_t* rep, int64_t i,
+                                                 bool in, int max_def, const NestThr& th) {
+  return nest_pred_of<K>(in ? (def ? (int)def[i] : 0) : -1, in ? (rep ? (int)rep[i] : 0) : 255, max_def, th);
+}
+
+template <int K>
+__global__ void __launch_bounds__(256) k_nest_count(const uint8_t* def_, const uint8_t* rep_, int64_t n, int max_def,
+                                                    NestThr th, int64_t nseg, int64_t* seg_cnt) {
+  constexpr int C = 2 * K + 2;
+  const PQG_G uint8_t* def = gconst(def_);
+  const PQG_G uint8_t* rep = gconst(rep_);
+  const int64_t seg = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (seg >= nseg) return;
+  const int lane = lane64();
+  const int64_t s0 = seg * kAsmSeg, s1 = s0 + kAsmSeg < n ? s0 + kAsmSeg : n;
+  int cnt[C];
+#pragma unroll
+  for (int j = 0; j < C; j++) cnt[j] = 0;
+  auto count = [&](const NestPred<K>& p) {  // one 64-slot ballot
+#pragma unroll
+    for (int k = 0; k <= K; k++) cnt[k] += __popcll(ballot64(p.e[k]));
+    cnt[K + 1] += __popcll(ballot64(p.valid));
+#pragma unroll
+    for (int k = 1; k <= K; k++) cnt[K + 1 + k] += __popcll(ballot64(p.e[k - 1] && p.d < th.list_def[k - 1]));
+  };
+  int64_t b = s0;
+  // a dword of each stream per lane, four ballots from it (counts do not care
+  // which slot a lane holds): whole 256-slot groups of 4-byte-aligned streams
+  // (a segment starts at a multiple of 4096)
+  if ((((uintptr_t)def_ | (uintptr_t)rep_) & 3) == 0) {
+    for (; b + 256 <= s1; b += 256) {
+      const int64_t q = (b >> 2) + lane;
+      const uint32_t dw = def ? ((const PQG_G uint32_t*)def)[q] : 0u;
+      const uint32_t rw = rep ? ((const PQG_G uint32_t*)rep)[q] : 0u;
+#pragma unroll
+      for (int j = 0; j < 4; j++)
+        count(nest_pred_of<K>((int)((dw >> (8 * j)) & 0xffu), (int)((rw >> (8 * j)) & 0xffu), max_def, th));
+    }
+  }
+  for (; b < s1; b += 64) count(nest_pred<K>(def, rep, b + lane, b + lane < s1, max_def, th));
+  if (lane == 0) {
+    PQG_G int64_t* o = gmut(seg_cnt) + C * seg;
+#pragma unroll
+    for (int j = 0; j < C; j++) o[j] = cnt[j];
+  }
+}
+
+// Exclusive scan of the C per-segment counters in place; tot[0..C-1] = totals.
+// One block, 1024 segments a round: a shuffle scan inside each wave, the 16
+// wave sums through LDS, and a carry from round to round.  Writes no output.
+template <int C>
+__global__ void __launch_bounds__(1024) k_nest_scan(int64_t* seg_cnt, int64_t nseg, int64_t* tot) {
+  __shared__ int64_t wsum[C][16];
+  __shared__ int64_t carry[C];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  if (t < C) carry[t] = 0;
+  __syncthreads();
+  for (int64_t base = 0; base < nseg; base += 1024) {
+    const int64_t k = base + t;
+    int64_t v[C], inc[C];
+#pragma unroll
+    for (int j = 0; j < C; j++) {
+      v[j] = k < nseg ? seg_cnt[C * k + j] : 0;
+      inc[j] = v[j];
+#pragma unroll
+      for (int d = 1; d < 64; d <<= 1) {
+        const int64_t up = __shfl_up(inc[j], d);
+        if (lane >= d) inc[j] += up;
+      }
+      if (lane == 63) wsum[j][wave] = inc[j];
+    }
+    __syncthreads();
+    if (k < nseg) {
+#pragma unroll
+      for (int j = 0; j < C; j++) {
+        int64_t before = carry[j];
+        for (int w = 0; w < wave; w++) before += wsum[j][w];
+        seg_cnt[C * k + j] = before + inc[j] - v[j];
+      }
+    }
+    __syncthreads();
+    if (t < C) {
+      int64_t s = 0;
+      for (int w = 0; w < 16; w++) s += wsum[t][w];
+      carry[t] += s;
+    }
+    __syncthreads();
+  }
+  if (t < C) tot[t] = carry[t];
+}
+
+template <int K, int W>
+__global__ void __launch_bounds__(256) k_nest_write(const uint8_t* def_, const uint8_t* rep_, const uint8_t* values_,
+                                                    const int64_t* value_offsets_, int64_t n, int max_def, NestThr th,
+                                                    int w, int64_t nseg, const int64_t* seg_cnt, const int64_t* tot_,
+                                                    NestOut out, uint8_t* leaf_validity_, uint8_t* leaf_values_,
+                                                    int64_t* leaf_offsets_) {
+  constexpr int C = 2 * K + 2;
+  const PQG_G uint8_t* def = gconst(def_);
+  const PQG_G uint8_t* rep = gconst(rep_);
+  const PQG_G uint8_t* values = gconst(values_);
+  const PQG_G int64_t* value_offsets = gconst(value_offsets_);
+  PQG_G uint8_t* leaf_values = gmut(leaf_values_);
+  PQG_G int64_t* leaf_offsets = gmut(leaf_offsets_);
+  uint32_t* lvalid = (uint32_t*)leaf_validity_;
+  const int64_t seg = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (seg >= nseg) return;
+  const int lane = lane64();
+  if (seg == 0 && lane == 0) {  // the closing offsets, from the totals
+    const PQG_G int64_t* tot = gconst(tot_);
+#pragma unroll
+    for (int k = 1; k <= K; k++)
+      if (out.offsets[k - 1]) gmut(out.offsets[k - 1])[tot[k - 1]] = (int32_t)tot[k];
+    if (leaf_offsets) leaf_offsets[tot[K]] = value_offsets[tot[K + 1]];
+  }
+  const uint64_t lt = lane ? (~0ull >> (64 - lane)) : 0ull;
+  const int64_t s0 = seg * kAsmSeg, s1 = s0 + kAsmSeg < n ? s0 + kAsmSeg : n;
+  const PQG_G int64_t* sc = gconst(seg_cnt) + C * seg;
+  int64_t base[K + 1];  // elements of each depth before this ballot
+#pragma unroll
+  for (int k = 0; k <= K; k++) base[k] = sc[k];
+  int64_t vb = sc[K + 1];
+  // one 64-slot ballot: this lane's slot has predicates p
+  auto emit = [&](const NestPred<K>& p) {
+    uint64_t m[K + 1];
+#pragma unroll
+    for (int k = 0; k <= K; k++) m[k] = ballot64(p.e[k]);
+    const uint64_t mv = ballot64(p.valid);
+#pragma unroll
+    for (int k = 1; k <= K; k++) {  // the depth-k lists entered at e[k-1]
+      PQG_G int32_t* off = gmut(out.offsets[k - 1]);
+      if (off && p.e[k - 1]) off[base[k - 1] + __popcll(m[k - 1] & lt)] = (int32_t)(base[k] + __popcll(m[k] & lt));
+      if (out.validity[k - 1]) {
+        const uint64_t bits = compress_ballot(p.e[k - 1] && p.d >= th.list_def[k - 1], p.e[k - 1], m[k - 1], lt);
+        if (lane == 0) or_bits(out.validity[k - 1], base[k - 1], bits);
+      }
+    }
+    const int64_t le = base[K] + __popcll(m[K] & lt);  // leaf slot
+    const int64_t vr = vb + __popcll(mv & lt);         // dense value cursor
+    if (p.e[K]) {
+      if (leaf_values) copy_value<W>(leaf_values + le * w, values + vr * w, p.valid, w);
+      if (leaf_offsets) leaf_offsets[le] = value_offsets[vr];
+    }
+    if (leaf_validity_) {
+      const uint64_t bits = compress_ballot(p.e[K] && p.valid, p.e[K], m[K], lt);
+      if (lane == 0) or_bits(lvalid, base[K], bits);
+    }
+#pragma unroll
+    for (int k = 0; k <= K; k++) base[k] += __popcll(m[k]);
+    vb += __popcll(mv);
+  };
+  int64_t b = s0;
+  // a dword of each stream per lane, handed round so that lane l of ballot j
+  // holds slot b + 64 j + l (byte l & 3 of lane 16 j + l / 4): whole 256-slot
+  // groups of 4-byte-aligned streams
+  if ((((uintptr_t)def_ | (uintptr_t)rep_) & 3) == 0) {
+    for (; b + 256 <= s1; b += 256) {
+      const int64_t q = (b >> 2) + lane;
+      const int dw = def ? (int)((const PQG_G uint32_t*)def)[q] : 0;
+      const int rw = rep ? (int)((const PQG_G uint32_t*)rep)[q] : 0;
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        const int from = (16 * j + (lane >> 2)) << 2, sh = 8 * (lane & 3);
+        const int d = (__builtin_amdgcn_ds_bpermute(from, dw) >> sh) & 0xff;
+        const int r = (__builtin_amdgcn_ds_bpermute(from, rw) >> sh) & 0xff;
+        emit(nest_pred_of<K>(d, r, max_def, th));
+      }
+    }
+  }
+  for (; b < s1; b += 64) emit(nest_pred<K>(def, rep, b + lane, b + lane < s1, max_def, th));
+}
+
+static NestThr nest_thresholds(const pqg_nested_args* a) {
+  NestThr th;
+  for (int k = 0; k < PQG_MAX_LIST_DEPTH; k++) {
+    th.list_def[k] = k < a->depth ? a->level[k].list_def : 0;
+    th.elem_def[k] = k < a->depth ? a->level[k].elem_def : 0;
+  }
+  return th;
+}
+
+// Count + scan of the nested export; tot[0..2K+1] = rows, e_1..e_K, valid
+// leaves, null lists of depth 1..K.  Writes no output.
+int nested_count_launch(hipStream_t s, const pqg_nested_args* a, int64_t* seg_scratch, int64_t* tot) {
+  const int64_t n = a->num_slots;
+  const int64_t nseg = (n + kAsmSeg - 1) / kAsmSeg;
+  const unsigned blocks = (unsigned)((nseg + 3) / 4);
+  const NestThr th = nest_thresholds(a);
+#define PQG_NCNT(KK)                                                                                                \
+  do {                                                                                                              \
+    if (nseg > 0)                                                                                                   \
+      hipLaunchKernelGGL(k_nest_count<KK>, dim3(blocks), dim3(256), 0, s, a->def_levels, a->rep_levels, n,          \
+                         a->max_def, th, nseg, seg_scratch);                                                        \
+    hipLaunchKernelGGL(k_nest_scan<2 * KK + 2>, dim3(1), dim3(1024), 0, s, seg_scratch, nseg, tot);                 \
+  } while (0)
+  switch (a->depth) {
+    case 0: PQG_NCNT(0); break;
+    case 1: PQG_NCNT(1); break;
+    case 2: PQG_NCNT(2); break;
+    case 3: PQG_NCNT(3); break;
+    default: PQG_NCNT(4); break;
+  }
+#undef PQG_NCNT
+  return hipGetLastError() == hipSuccess ? PQG_OK : PQG_ERR_HIP;
+}
+
+template <int K>
+static void nested_write_k(hipStream_t s, const pqg_nested_args* a, const NestThr& th, const NestOut& out, int w,
+                           int64_t nseg, const int64_t* seg_scratch, const int64_t* tot) {
+  const unsigned blocks = (unsigned)((nseg + 3) / 4);
+#define PQG_NST(WW)                                                                                                  \
+  hipLaunchKernelGGL((k_nest_write<K, WW>), dim3(blocks), dim3(256), 0, s, a->def_levels, a->rep_levels, a->values, \
+                     a->value_offsets, a->num_slots, a->max_def, th, w, nseg, seg_scratch, tot, out,                \
+                     a->leaf_validity, a->leaf_values, a->leaf_offsets)
+  switch (w) {
+    case 1: PQG_NST(1); break;
+    case 4: PQG_NST(4); break;
+    case 8: PQG_NST(8); break;
+    default: PQG_NST(0); break;
+  }
+#undef PQG_NST
+}
+
+// The outputs, after nested_count_launch's totals were checked by the host.
+int nested_write_launch(hipStream_t s, const pqg_nested_args* a, int64_t* seg_scratch, const int64_t* tot) {
+  const int64_t n = a->num_slots;
+  const int64_t nseg = (n + kAsmSeg - 1) / kAsmSeg;
+  const int w = a->leaf_values ? a->value_width : 0;
+  const size_t bm_bytes = (size_t)((n + 31) / 32) * 4;  // whole dwords (see pqgpu.h)
+  const NestThr th = nest_thresholds(a);
+  NestOut out;
+  for (int k = 0; k < PQG_MAX_LIST_DEPTH; k++) {
+    out.validity[k] = k < a->depth ? (uint32_t*)a->level[k].validity : nullptr;
+    out.offsets[k] = k < a->depth ? a->level[k].offsets : nullptr;
+    if (out.validity[k] && bm_bytes) hipMemsetAsync(out.validity[k], 0, bm_bytes, s);
+  }
+  if (a->leaf_validity && bm_bytes) hipMemsetAsync(a->leaf_validity, 0, bm_bytes, s);
+  if (nseg == 0) {  // no slot: only the closing offsets (all zero)
+    for (int k = 0; k < a->depth; k++)
+      if (out.offsets[k]) hipMemsetAsync(out.offsets[k], 0, sizeof(int32_t), s);
+    if (a->leaf_offsets)
+      hipMemcpyAsync(a->leaf_offsets, a->value_offsets, sizeof(int64_t), hipMemcpyDeviceToDevice, s);
+    return hipGetLastError() == hipSuccess ? PQG_OK : PQG_ERR_HIP;
+  }
+  switch (a->depth) {
+    case 0: nested_write_k<0>(s, a, th, out, w, nseg, seg_scratch, tot); break;
+    case 1: nested_write_k<1>(s, a, th, out, w, nseg, seg_scratch, tot); break;
+    case 2: nested_write_k<2>(s, a, th, out, w, nseg, seg_scratch, tot); break;
+    case 3: nested_write_k<3>(s, a, th, out, w, nseg, seg_scratch, tot); break;
+    default: nested_write_k<4>(s, a, th, out, w, nseg, seg_scratch, tot); break;
+  }
+  return hipGetLastError() == hipSuccess ? PQG_OK : PQG_ERR_HIP;
+}
+
+// ---------------------------------------------------------------------------
 // ColumnStore refill: levels -> packedArray bytes (packed_array.go:34-101).
 // One lane per group of 8 levels: one 8-byte load, the 8 w-bit fields OR-ed
 // into a 64-bit word (bw <= 8 for u8 levels), bw byte stores.

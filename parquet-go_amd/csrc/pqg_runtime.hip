@@ -23,6 +23,8 @@ namespace pqg {
 int assemble_launch(hipStream_t s, const pqg_assemble_args* a, int64_t* seg_scratch, int64_t* tot);  // pqg_assemble.hip
 int list_count_launch(hipStream_t s, const pqg_list_args* a, int64_t* seg_scratch, int64_t* tot);    // pqg_assemble.hip
 int list_write_launch(hipStream_t s, const pqg_list_args* a, int64_t* seg_scratch);                  // pqg_assemble.hip
+int nested_count_launch(hipStream_t s, const pqg_nested_args* a, int64_t* seg_scratch, int64_t* tot);  // pqg_assemble.hip
+int nested_write_launch(hipStream_t s, const pqg_nested_args* a, int64_t* seg_scratch, const int64_t* tot);  // pqg_assemble.hip
 int pack_levels_launch(hipStream_t s, const uint8_t* levels, int64_t n, int bw, uint8_t* packed);     // pqg_assemble.hip
 }
 
@@ -844,6 +846,59 @@ int pqg_assemble_list(pqg_ctx* c, pqg_list_args* a) {
   if (h[1] > INT32_MAX) return PQG_ERR_INVALID_ARG;
   hipEventRecord(c->ev_k8[2], c->stream);
   e = pqg::list_write_launch(c->stream, a, seg);
+  if (e) return e;
+  hipEventRecord(c->ev_k8[3], c->stream);
+  e = hip_ok(hipStreamSynchronize(c->stream));
+  float m0 = 0.f, m1 = 0.f;
+  hipEventElapsedTime(&m0, c->ev_k8[0], c->ev_k8[1]);
+  hipEventElapsedTime(&m1, c->ev_k8[2], c->ev_k8[3]);
+  c->k8_ms = m0 + m1;
+  return e;
+}
+
+// Nested export: replaces the getData / getNextData recursion (schema.go:171-264)
+// over ColumnStore.get (data_store.go:158-203) for a leaf under `depth` lists.
+int pqg_assemble_nested(pqg_ctx* c, pqg_nested_args* a) {
+  if (!c || !a) return PQG_ERR_INVALID_ARG;
+  if (a->depth < 0 || a->depth > PQG_MAX_LIST_DEPTH) return PQG_ERR_UNSUPPORTED;
+  if (a->num_slots < 0 || a->max_def < 0 || a->max_def > 255 || a->value_width < 0) return PQG_ERR_INVALID_ARG;
+  if (!a->def_levels && a->max_def > 0) return PQG_ERR_INVALID_ARG;
+  const int K = a->depth;
+  int prev = 0;  // elem_def[k-1] <= list_def[k] <= elem_def[k] <= max_def, elem_def strictly increasing
+  for (int k = 0; k < K; k++) {
+    const pqg_nested_level& l = a->level[k];
+    if (l.list_def < prev || l.elem_def < l.list_def || l.elem_def <= prev || l.elem_def > a->max_def)
+      return PQG_ERR_INVALID_ARG;
+    prev = l.elem_def;
+  }
+  if (a->leaf_values && (a->value_width <= 0 || !a->values)) return PQG_ERR_INVALID_ARG;
+  if (a->leaf_offsets && !a->value_offsets) return PQG_ERR_INVALID_ARG;
+  hipSetDevice(c->device);
+  const int C = 2 * K + 2;
+  const int64_t nseg = (a->num_slots + 4095) / 4096;
+  if (c->asm_seg.grow((size_t)(C * nseg + C) * sizeof(int64_t))) return PQG_ERR_HIP;
+  int64_t* seg = (int64_t*)c->asm_seg.p;
+  int64_t* tot = seg + C * nseg;
+  hipEventRecord(c->ev_k8[0], c->stream);
+  int e = pqg::nested_count_launch(c->stream, a, seg, tot);
+  if (e) return e;
+  hipEventRecord(c->ev_k8[1], c->stream);
+  int64_t h[2 * PQG_MAX_LIST_DEPTH + 2] = {0};
+  if (hipMemcpyAsync(h, tot, (size_t)C * sizeof(int64_t), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+      hipStreamSynchronize(c->stream) != hipSuccess)
+    return PQG_ERR_HIP;
+  // int32 offsets cannot hold some depth's elements: fail before any output is written
+  for (int k = 1; k <= K; k++)
+    if (h[k] > INT32_MAX) return PQG_ERR_INVALID_ARG;
+  a->num_rows = h[0];
+  a->num_leaf = h[K];
+  a->num_valid = h[K + 1];
+  for (int k = 0; k < K; k++) {
+    a->level[k].num_entries = h[k];
+    a->level[k].null_count = h[K + 2 + k];
+  }
+  hipEventRecord(c->ev_k8[2], c->stream);
+  e = pqg::nested_write_launch(c->stream, a, seg, tot);
   if (e) return e;
   hipEventRecord(c->ev_k8[3], c->stream);
   e = hip_ok(hipStreamSynchronize(c->stream));

@@ -163,5 +163,24 @@ class ListArgs(C.Structure):
                 ("null_lists", C.c_int64)]
 
 
+MAX_LIST_DEPTH = 4
+
+
+class NestedLevel(C.Structure):
+    """pqg_nested_level (include/pqgpu.h, K8 nested export)."""
+    _fields_ = [("list_def", C.c_int32), ("elem_def", C.c_int32), ("validity", C.c_void_p),
+                ("offsets", C.c_void_p), ("num_entries", C.c_int64), ("null_count", C.c_int64)]
+
+
+class NestedArgs(C.Structure):
+    """pqg_nested_args (include/pqgpu.h, K8 nested export)."""
+    _fields_ = [("def_levels", C.c_void_p), ("rep_levels", C.c_void_p), ("values", C.c_void_p),
+                ("value_offsets", C.c_void_p), ("num_slots", C.c_int64),
+                ("max_def", C.c_int32), ("depth", C.c_int32), ("value_width", C.c_int32), ("reserved", C.c_int32),
+                ("level", NestedLevel * MAX_LIST_DEPTH),
+                ("leaf_validity", C.c_void_p), ("leaf_values", C.c_void_p), ("leaf_offsets", C.c_void_p),
+                ("num_rows", C.c_int64), ("num_leaf", C.c_int64), ("num_valid", C.c_int64)]
+
+
 def status_name(code):
     return STATUS.get(int(code), str(code))

@@ -291,6 +291,74 @@ class GpuDecoder:
         _check(self.L.pqg_assemble_list(self.ctx, C.byref(a)), "pqg_assemble_list")
         return a, a.list_validity, a.list_offsets, a.elem_validity, a.elem_values
 
+    def assemble_nested(self, def_ptr, rep_ptr, values_ptr, num_slots, max_def, list_def=(), elem_def=(),
+                        value_width=0, value_offsets_ptr=None, validity=True, offsets=True, leaf_validity=True,
+                        values=True):
+        """K8 nested export (Arrow layout of every list depth) of device
+        level/value arrays; the counterpart of assemble_list for any depth and
+        for byte-array leaves (value_offsets_ptr: the chunk result's offsets).
+        Allocates the requested outputs and returns the NestedArgs, whose
+        level[k].validity / offsets, leaf_validity, leaf_values and
+        leaf_offsets are the device pointers."""
+        depth = len(elem_def)
+        if depth > abi.MAX_LIST_DEPTH:
+            raise PqgError(abi.STATUS_CODES["UNSUPPORTED"], "pqg_assemble_nested: %d list depths" % depth)
+        a = abi.NestedArgs()
+        a.def_levels, a.rep_levels, a.values = def_ptr or None, rep_ptr or None, values_ptr or None
+        a.value_offsets = value_offsets_ptr or None
+        a.num_slots, a.max_def, a.depth, a.value_width = num_slots, max_def, depth, value_width
+
+        def alloc(nbytes):
+            p = C.c_void_p()
+            _check(self.L.pqg_device_alloc(self.ctx, max(nbytes, 1), C.byref(p)), "pqg_device_alloc")
+            self._bufs.append(p)
+            return p.value
+
+        bm = (num_slots + 31) // 32 * 4
+        for k in range(depth):
+            a.level[k].list_def, a.level[k].elem_def = list_def[k], elem_def[k]
+            a.level[k].validity = alloc(bm) if validity else None
+            a.level[k].offsets = alloc((num_slots + 1) * 4) if offsets else None
+        a.leaf_validity = alloc(bm) if leaf_validity else None
+        if values and value_offsets_ptr:
+            a.leaf_offsets = alloc((num_slots + 1) * 8)
+        elif values and value_width:
+            a.leaf_values = alloc(num_slots * value_width)
+        try:
+            _check(self.L.pqg_assemble_nested(self.ctx, C.byref(a)), "pqg_assemble_nested")
+        except PqgError:
+            self.free_nested(a)
+            raise
+        return a
+
+    def free_nested(self, a):
+        """Free the outputs assemble_nested allocated."""
+        for p in [a.leaf_validity, a.leaf_values, a.leaf_offsets] + \
+                 [x for k in range(a.depth) for x in (a.level[k].validity, a.level[k].offsets)]:
+            if p:
+                self.free(p)
+
+    def last_assemble_ms(self):
+        ms = C.c_float()
+        _check(self.L.pqg_last_assemble_ms(self.ctx, C.byref(ms)), "pqg_last_assemble_ms")
+        return ms.value
+
+    def download_nested(self, a, chars=None, physical_type=None, flags=0):
+        """The outputs of an assemble_nested call as a NestedColumn on the host
+        (`chars`: the decoded chars of a byte-array leaf, already downloaded)."""
+        from .nested import NestedColumn
+        levels = []
+        for k in range(a.depth):
+            l = a.level[k]
+            offs = self.d2h(l.offsets, (l.num_entries + 1) * 4, np.int32) if l.offsets else None
+            val = self.d2h(l.validity, (l.num_entries + 31) // 32 * 4, np.uint32) if l.validity else None
+            levels.append((offs, val, int(l.null_count)))
+        lv = self.d2h(a.leaf_validity, (a.num_leaf + 31) // 32 * 4, np.uint32) if a.leaf_validity else None
+        vals = self.d2h(a.leaf_values, a.num_leaf * a.value_width) if a.leaf_values else None
+        lo = self.d2h(a.leaf_offsets, (a.num_leaf + 1) * 8, np.int64) if a.leaf_offsets else None
+        return NestedColumn(levels, lv, int(a.num_leaf), values=vals, value_width=a.value_width, chars=chars,
+                            leaf_offsets=lo, physical_type=physical_type, flags=flags, num_rows=int(a.num_rows))
+
     def download(self, r, job_index=None):
         lv_def = self.d2h(r.def_levels, r.num_slots) if (r.def_levels and r.status == 0) else None
         lv_rep = self.d2h(r.rep_levels, r.num_slots) if (r.rep_levels and r.status == 0) else None
@@ -459,6 +527,45 @@ class FileReader:
         try:
             return {self.file.columns[c].path.decode(): self.dec.download(r, i)
                     for i, ((_, c), r) in enumerate(zip(specs, res))}
+        finally:
+            self.dec.free(dev)
+
+    def read_row_group_nested(self, rg):
+        """One row group's selected columns in Arrow layout: {path:
+        NestedColumn} (pqgpu.nested).  Each chunk is decoded on the GPU, its
+        device levels and values go through pqg_assemble_nested with the
+        thresholds of the leaf's path (nested.leaf_thresholds), and only the
+        Arrow buffers are downloaded: no level leaves the device.  A leaf under
+        more than abi.MAX_LIST_DEPTH lists raises PqgError(UNSUPPORTED)."""
+        from .nested import leaf_thresholds
+        specs = [(rg, c) for c in self.selected]
+        if not specs:
+            return {}
+        thr = {}
+        for _, c in specs:  # before any decode: an unsupported depth costs no GPU work
+            ld, ed = leaf_thresholds(self.file.schema_nodes, c)
+            if len(ed) > abi.MAX_LIST_DEPTH:
+                raise PqgError(abi.STATUS_CODES["UNSUPPORTED"], "column %s: %d list depths (at most %d)"
+                               % (self.file.columns[c].path.decode(), len(ed), abi.MAX_LIST_DEPTH))
+            thr[c] = (ld, ed)
+        res, dev, nbytes = decode_spans(self.file, specs, self.dec)
+        self.uploaded_bytes += nbytes
+        out = {}
+        try:
+            for (_, c), r in zip(specs, res):
+                path = self.file.columns[c].path.decode()
+                if r.status != 0:
+                    raise PqgError(r.status, "column %s of row group %d" % (path, rg))
+                desc = self.file.columns[c].desc
+                ld, ed = thr[c]
+                a = self.dec.assemble_nested(r.def_levels, r.rep_levels, r.values, r.num_slots, desc.max_def, ld, ed,
+                                             value_width=r.value_width, value_offsets_ptr=r.offsets)
+                try:
+                    chars = self.dec.d2h(r.values, r.values_bytes) if r.offsets else None
+                    out[path] = self.dec.download_nested(a, chars, desc.physical_type, desc.flags)
+                finally:
+                    self.dec.free_nested(a)
+            return out
         finally:
             self.dec.free(dev)
 
