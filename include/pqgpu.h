@@ -59,7 +59,8 @@ enum {
 enum {
   PQG_CODEC_UNCOMPRESSED = 0,
   PQG_CODEC_SNAPPY = 1,
-  PQG_CODEC_GZIP = 2
+  PQG_CODEC_GZIP = 2,
+  PQG_CODEC_ZSTD = 6          /* parquet's CompressionCodec number, as 1 and 2 are */
 };
 enum {
   PQG_PAGE_DATA = 0,
@@ -90,6 +91,7 @@ enum {
   PQG_ERR_BYTE_ARRAY = -12,   /* bytearray/plain: negative length                   */
   PQG_ERR_LEVELS = -13,       /* level decoder not initialised (V2, zero length)    */
   PQG_ERR_GZIP = -15,         /* gzip: invalid header / data / checksum (compress.go:63-76) */
+  PQG_ERR_ZSTD = -16,         /* zstd: invalid frame / block / checksum             */
   PQG_ERR_FIXED_LEN = -14,    /* DELTA_BYTE_ARRAY on FIXED_LEN_BYTE_ARRAY: a value  */
                               /* whose length is not type_length (the reference     */
                               /* returns it; the fixed-width output cannot hold it) */
@@ -252,8 +254,11 @@ int pqg_decode_page(pqg_ctx* ctx, const pqg_page_job* job, pqg_chunk_result* res
  * synchronously on the GPU.  codec SNAPPY (snappy.Decode semantics: decoded
  * length from the block's varint header, ErrCorrupt -> PQG_ERR_SNAPPY), GZIP
  * (gzipCompressor.DecompressBlock, compress.go:63-76: multistream members,
- * a bad header / block / CRC / ISIZE or trailing bytes -> PQG_ERR_GZIP) or
- * UNCOMPRESSED (a copy).  *out_len is the decoded length; PQG_ERR_CAPACITY
+ * a bad header / block / CRC / ISIZE or trailing bytes -> PQG_ERR_GZIP), ZSTD
+ * (libzstd's ZSTD_decompress over the whole block: any number of frames and
+ * skippable frames, content checksums verified, no dictionaries; an invalid
+ * frame / block / checksum, a content size that differs from the decoded one
+ * or trailing bytes -> PQG_ERR_ZSTD) or UNCOMPRESSED (a copy).  *out_len is the decoded length; PQG_ERR_CAPACITY
  * when it exceeds `cap` (nothing written). */
 int pqg_block_decompress(pqg_ctx* ctx, int codec, const uint8_t* src, int64_t n, uint8_t* dst, int64_t cap,
                          int64_t* out_len);

@@ -18,6 +18,7 @@
 
 #include "../../include/pqgpu.h"
 #include "pqg_common.h"
+#include "pqg_zstd.h"
 
 namespace pqg {
 int assemble_launch(hipStream_t s, const pqg_assemble_args* a, int64_t* seg_scratch, int64_t* tot);  // pqg_assemble.hip
@@ -48,6 +49,8 @@ __global__ void k_snappy(JobDev* jobs, PageDev* pages, const int* list, const in
                          uint8_t* scratch);
 __global__ void k_inflate(JobDev* jobs, PageDev* pages, const int* list, const int* total, int* queue,
                           uint8_t* scratch, int mode);
+__global__ void k_zstd(JobDev* jobs, PageDev* pages, const int* list, const int* total, int* queue, uint8_t* scratch,
+                       uint8_t* wspace);
 __global__ void k_inflate_s(JobDev* jobs, PageDev* pages, const int* list, const int* total, int* queue,
                             uint8_t* scratch);
 __global__ void k_snap_plan(const JobDev* jobs, PageDev* pages, const int* list, const int* total, int* ctr,
@@ -177,6 +180,9 @@ int value_width_of(const pqg_column_desc& c) {
 
 }  // namespace
 
+struct pqg_ctx;
+static unsigned zstd_grid(const pqg_ctx* c);
+
 struct pqg_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -193,6 +199,8 @@ struct pqg_ctx {
   int link_waves = 16;    // PQG_LINK_WAVES: k_snap_link waves per CU (one wave per big page; 4: C4 +50 %)
   int snappy_per_cu = 2;  // resident k_snappy waves per CU (LDS-bound: the output history ring)
   int inflate_per_cu = 8; // resident k_inflate_s waves per CU (LDS / VGPR bound), from the occupancy query
+  int zstd_per_cu = 8;    // resident k_zstd waves per CU (LDS-bound: its tables), from the occupancy query
+  DevBuf zstd_ws;         // k_zstd: a literal workspace (zstd::kWsBytes) per wave of its grid
   DevBuf jobs, pages, list, counters, def_arena, rep_arena, value_arena, scratch;
   DevBuf tile_job;  // K1: tile -> job
   DevBuf tile_count, tile_okc, tile_off, tile_okoff, cand_pos, cands, succ, idx2slot, ok2slot, order;  // K1
@@ -258,6 +266,7 @@ const char* pqg_status_string(int s) {
     case PQG_ERR_LEVELS: return "level reader is not initialized";
     case PQG_ERR_FIXED_LEN: return "bytearray/delta: value length is not the fixed length";
     case PQG_ERR_GZIP: return "gzip: invalid data";
+    case PQG_ERR_ZSTD: return "zstd: invalid frame / block / checksum";
     case PQG_ERR_CAPACITY: return "capacity";
     case PQG_ERR_INVALID_ARG: return "invalid argument";
     case PQG_ERR_HIP: return "HIP runtime error";
@@ -307,6 +316,10 @@ int pqg_ctx_create(int device, pqg_ctx** out) {
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void*>(&k_inflate_s), 64, 0) ==
           hipSuccess && occ > 0)
     c->inflate_per_cu = occ;
+  occ = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void*>(&k_zstd), 64, 0) ==
+          hipSuccess && occ > 0)
+    c->zstd_per_cu = occ;
   // counters: ctr[0..1023] + the kQShards-sharded work queues and the per-stage flags
   if (c->counters.grow(sizeof(int) * (size_t)(1024 + kQueueSlots * kQueueInts))) {
     pqg_ctx_destroy(c);
@@ -327,7 +340,7 @@ void pqg_ctx_destroy(pqg_ctx* c) {
                     &c->ok2slot, &c->order, &c->asm_seg, &c->offs_arena, &c->doffs_arena, &c->page_stage,
                     &c->blk_src, &c->blk_dst, &c->blk_meta, &c->tile_job, &c->sn_subs, &c->sn_segpage, &c->sn_F,
                     &c->blk_subs, &c->blk_segpage, &c->blk_F, &c->vrecs, &c->parts, &c->lev_long, &c->lev_pieces,
-                    &c->walk_long, &c->nn_sums, &c->nn_jobs})
+                    &c->walk_long, &c->nn_sums, &c->nn_jobs, &c->zstd_ws})
     b->release();
   if (c->h_jobs) hipHostFree(c->h_jobs);
   hipStreamDestroy(c->stream);
@@ -369,6 +382,7 @@ static int plan_batch(pqg_ctx* c) {
   }
   int64_t page_total = 0, slot_total = 0, value_total = 0, scratch_total = 0, tile_total = 0, run_total = 0,
           blk_total = 0, offs_total = 0, doffs_total = 0, seg_total = 0;
+  bool any_zstd = false;
   c->plan.resize((size_t)n);
   for (int i = 0; i < n; i++) {
     const pqg_chunk_job& in = c->cur[(size_t)i];
@@ -414,6 +428,7 @@ static int plan_batch(pqg_ctx* c) {
     d.scratch_base = scratch_total;
     scratch_total += align_up(xcap, 256);
     if (in.col.codec != PQG_CODEC_UNCOMPRESSED) seg_total += in.total_compressed_size / kSnapSeg + pcap;
+    any_zstd |= in.col.codec == PQG_CODEC_ZSTD;
     d.dict_page = -1;
     d.error_page = -1;
     const int64_t lim = std::max<int64_t>(0, std::min(in.total_compressed_size, in.data_len));
@@ -466,6 +481,8 @@ static int plan_batch(pqg_ctx* c) {
   // and a block of b bytes ceil(b / 4 KiB) segments
   c->sn_sub_cap = scratch_total / kSnapSub + page_total + 64;
   c->sn_seg_cap = seg_total + 64;
+  // k_zstd: one literal workspace per wave of its grid
+  if (any_zstd && c->zstd_ws.grow((size_t)zstd_grid(c) * zstd::kWsBytes)) return PQG_ERR_HIP;
   if (c->sn_subs.grow(sizeof(SnapSub) * (size_t)c->sn_sub_cap) || c->sn_segpage.grow(sizeof(int) * (size_t)c->sn_seg_cap) ||
       c->sn_F.grow(sizeof(uint2) * 64 * (size_t)c->sn_seg_cap))
     return PQG_ERR_HIP;
@@ -528,6 +545,8 @@ static void launch_snappy(pqg_ctx* c, hipStream_t s, JobDev* jobs, PageDev* page
   hipLaunchKernelGGL(k_snappy, dim3(qgrid(waves)), dim3(64), 0, s, jobs, pages, list, total, q_serial, scratch);
 }
 
+static unsigned zstd_grid(const pqg_ctx* c) { return qgrid((int64_t)c->num_cus * c->zstd_per_cu); }
+
 static int launch_pipeline(pqg_ctx* c) {
   const int n = c->n_jobs;
   c->launches++;
@@ -581,10 +600,11 @@ static int launch_pipeline(pqg_ctx* c) {
   hipLaunchKernelGGL(k_page_list, page_grid, dim3(1024), 0, s, jobs, pages, n, list,
                      (int)std::min<int64_t>(c->list_cap, INT32_MAX), ctr, ctr + 8);
   if (c->timed) hipEventRecord(c->ev[2], s);
-  bool any_snappy = false, any_gzip = false;
+  bool any_snappy = false, any_gzip = false, any_zstd = false;
   for (int i = 0; i < n; i++) {
     any_snappy |= c->cur[(size_t)i].col.codec == PQG_CODEC_SNAPPY;
     any_gzip |= c->cur[(size_t)i].col.codec == PQG_CODEC_GZIP;
+    any_zstd |= c->cur[(size_t)i].col.codec == PQG_CODEC_ZSTD;
   }
   if (any_snappy) {
     const SnapTables T{(SnapSub*)c->sn_subs.p, (int)std::min<int64_t>(c->sn_sub_cap, INT32_MAX), (int*)c->sn_segpage.p,
@@ -597,6 +617,9 @@ static int launch_pipeline(pqg_ctx* c) {
     hipLaunchKernelGGL(k_inflate, dim3(qgrid(c->num_cus * 4)), dim3(64), 0, s, jobs, pages, list, ctr,
                        Q(kQueueInflateRedo), scratch, 1);
   }
+  if (any_zstd)  // one wave per ZSTD page (pqg_zstd.hip), each with its literal workspace (plan_batch)
+    hipLaunchKernelGGL(k_zstd, dim3(zstd_grid(c)), dim3(64), 0, s, jobs, pages, list, ctr, Q(kQueueZstd), scratch,
+                       (uint8_t*)c->zstd_ws.p);
   if (c->timed) hipEventRecord(c->ev[3], s);
   HStream* streams = (HStream*)c->streams.p;
   RunEnt* runs = (RunEnt*)c->runs.p;
@@ -1016,6 +1039,58 @@ static int block_inflate(pqg_ctx* c, const uint8_t* src, int64_t n, uint8_t* dst
   return PQG_OK;
 }
 
+// zstd's ZSTD_decompress over one host block.  The output buffer is sized
+// before the decode from the block itself (zstd::decoded_bound: the frames'
+// content sizes, or per block its size / the 128 KiB block maximum), so one
+// pass decodes it whatever `cap` is; k_zstd never stores past that buffer.
+static int block_zstd(pqg_ctx* c, const uint8_t* src, int64_t n, uint8_t* dst, int64_t cap, int64_t* out_len) {
+  hipSetDevice(c->device);
+  bool exact = false;
+  const int64_t store = zstd::decoded_bound(src, n, &exact);
+  if (store > INT32_MAX) return PQG_ERR_UNSUPPORTED;  // one block of >= 2 GiB
+  if (c->blk_src.grow((size_t)n + 64) || c->blk_dst.grow((size_t)store + 64) || c->zstd_ws.grow((size_t)zstd_grid(c) * zstd::kWsBytes) ||
+      c->blk_meta.grow(sizeof(JobDev) + sizeof(PageDev) + (4 + 2 * kQueueInts) * sizeof(int)))
+    return PQG_ERR_HIP;
+  JobDev jd;
+  memset(&jd, 0, sizeof(jd));
+  jd.data = (const uint8_t*)c->blk_src.p;
+  jd.data_len = n;
+  jd.tcs = n;
+  jd.codec = PQG_CODEC_ZSTD;
+  jd.scratch_cap = store + 16;
+  PageDev pd;
+  memset(&pd, 0, sizeof(pd));
+  pd.page_type = PQG_PAGE_DICTIONARY;  // no values-decoder check after the block
+  pd.flags = kPageBareBlock;
+  pd.csize = (int32_t)n;
+  pd.usize = (int32_t)store;
+  pd.read_status = kOK;
+  uint8_t* meta = (uint8_t*)c->blk_meta.p;
+  JobDev* djob = (JobDev*)meta;
+  PageDev* dpage = (PageDev*)(meta + sizeof(JobDev));
+  int* ints = (int*)(meta + sizeof(JobDev) + sizeof(PageDev));  // [0] list, [1] total, then the queue
+  int hi[2] = {0, 1};
+  if ((n && hipMemcpyAsync(c->blk_src.p, src, (size_t)n, hipMemcpyHostToDevice, c->stream) != hipSuccess) ||
+      hipMemcpyAsync(djob, &jd, sizeof(jd), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+      hipMemcpyAsync(dpage, &pd, sizeof(pd), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+      hipMemcpyAsync(ints, hi, sizeof(hi), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+      hipMemsetAsync(ints + 4, 0, sizeof(int) * kQueueInts, c->stream) != hipSuccess)
+    return PQG_ERR_HIP;
+  hipLaunchKernelGGL(k_zstd, dim3(qgrid(1)), dim3(64), 0, c->stream, djob, dpage, ints, ints + 1, ints + 4,
+                     (uint8_t*)c->blk_dst.p, (uint8_t*)c->zstd_ws.p);
+  if (hipGetLastError() != hipSuccess) return PQG_ERR_HIP;
+  if (hipMemcpyAsync(&pd, dpage, sizeof(PageDev), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+      hipStreamSynchronize(c->stream) != hipSuccess)
+    return PQG_ERR_HIP;
+  if (pd.read_status != kOK) return pd.read_status;
+  *out_len = pd.gz_len;
+  if (pd.gz_len > cap) return PQG_ERR_CAPACITY;
+  if (pd.gz_len && (hipMemcpyAsync(dst, c->blk_dst.p, (size_t)pd.gz_len, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+                    hipStreamSynchronize(c->stream) != hipSuccess))
+    return PQG_ERR_HIP;
+  return PQG_OK;
+}
+
 int pqg_block_decompress(pqg_ctx* c, int codec, const uint8_t* src, int64_t n, uint8_t* dst, int64_t cap,
                          int64_t* out_len) {
   if (!c || (!src && n > 0) || n < 0 || n > INT32_MAX || !out_len) return PQG_ERR_INVALID_ARG;
@@ -1027,6 +1102,7 @@ int pqg_block_decompress(pqg_ctx* c, int codec, const uint8_t* src, int64_t n, u
     return PQG_OK;
   }
   if (codec == PQG_CODEC_GZIP) return block_inflate(c, src, n, dst, cap, out_len);
+  if (codec == PQG_CODEC_ZSTD) return block_zstd(c, src, n, dst, cap, out_len);
   if (codec != PQG_CODEC_SNAPPY) return PQG_ERR_UNSUPPORTED;
   // decodedLen (decode.go:32-43): the varint header, on the host to size the output
   uint64_t v = 0;

@@ -42,6 +42,11 @@ struct WinSrc {
 //                     both paths share classify_page.
 // ============================================================================
 
+// codecs with a decompression stage (K2 snappy, K2g gzip, K2z zstd)
+__device__ __forceinline__ bool codec_supported(int codec) {
+  return codec == kCodecSnappy || codec == kCodecGzip || codec == kCodecZstd;
+}
+
 // Read-phase classification of one parsed header (readPages :216-272 with
 // dictPageReader.read page_dict.go:30-64, dataPageReaderV1.read
 // page_v1.go:79-108, dataPageReaderV2.read page_v2.go:73-129).  `dict_seen`:
@@ -71,7 +76,7 @@ __device__ __forceinline__ int classify_page(const JobDev& job, const PageHdr& h
     else if (h.csize < 0 || h.usize < 0) e = kPAGE_HEADER;
     else if (job.data_len - payload < (int64_t)h.csize) e = kSIZE;
     else if (job.codec == 0) { if (h.csize != h.usize) e = kSIZE; }
-    else if (job.codec == kCodecSnappy || job.codec == kCodecGzip) *comp = ((int64_t)h.usize + 15) & ~(int64_t)15;
+    else if (codec_supported(job.codec)) *comp = ((int64_t)h.usize + 15) & ~(int64_t)15;
     else e = kUNSUPPORTED;
     *next = payload + h.csize;
     if (e == kOK && job.has_dict_off) *next = job.data_page_offset;
@@ -87,7 +92,7 @@ __device__ __forceinline__ int classify_page(const JobDev& job, const PageHdr& h
     else if (h.csize < 0 || h.usize < 0) e = kPAGE_HEADER;
     else if (job.data_len - payload < (int64_t)h.csize) e = kSIZE;
     else if (job.codec == 0 && h.csize != h.usize) e = kSIZE;
-    else if (job.codec != 0 && job.codec != kCodecSnappy && job.codec != kCodecGzip) e = kUNSUPPORTED;
+    else if (job.codec != 0 && !codec_supported(job.codec)) e = kUNSUPPORTED;
     else if (job.codec == 0 && !values_supported(job.type, job.type_length, enc)) e = kUNSUPPORTED;
     if (e == kOK && job.codec != 0) *comp = ((int64_t)h.usize + 15) & ~(int64_t)15;
     *next = payload + h.csize;
@@ -106,7 +111,7 @@ __device__ __forceinline__ int classify_page(const JobDev& job, const PageHdr& h
     else if (cs < 0 || us < 0) e = kPAGE_HEADER;
     else if (job.data_len - body < (int64_t)cs) e = kSIZE;
     else if (job.codec == 0 && cs != us) e = kSIZE;
-    else if (job.codec != 0 && job.codec != kCodecSnappy && job.codec != kCodecGzip) e = kUNSUPPORTED;
+    else if (job.codec != 0 && !codec_supported(job.codec)) e = kUNSUPPORTED;
     if (e == kOK && job.codec != 0) *comp = ((int64_t)us + 15) & ~(int64_t)15;
     *next = body + cs;
   } else {

@@ -15,6 +15,7 @@ ENC_DELTA_LENGTH_BYTE_ARRAY = 6
 ENC_DELTA_BYTE_ARRAY = 7
 ENC_RLE_DICTIONARY = 8
 CODEC_UNCOMPRESSED, CODEC_SNAPPY, CODEC_GZIP = 0, 1, 2
+CODEC_ZSTD = 6
 PAGE_DATA, PAGE_INDEX, PAGE_DICTIONARY, PAGE_DATA_V2 = 0, 1, 2, 3
 
 STATUS = {
@@ -34,6 +35,7 @@ STATUS = {
     -13: "LEVELS",
     -14: "FIXED_LEN",
     -15: "GZIP",
+    -16: "ZSTD",
     -20: "CAPACITY",
     -21: "INVALID_ARG",
     -22: "HIP",
