@@ -60,7 +60,8 @@ enum {
   PQG_CODEC_UNCOMPRESSED = 0,
   PQG_CODEC_SNAPPY = 1,
   PQG_CODEC_GZIP = 2,
-  PQG_CODEC_ZSTD = 6          /* parquet's CompressionCodec number, as 1 and 2 are */
+  PQG_CODEC_ZSTD = 6,         /* parquet's CompressionCodec number, as 1 and 2 are */
+  PQG_CODEC_LZ4_RAW = 7       /* one bare LZ4 block per page; 5, the Hadoop-framed LZ4, is unsupported */
 };
 enum {
   PQG_PAGE_DATA = 0,
@@ -92,6 +93,7 @@ enum {
   PQG_ERR_LEVELS = -13,       /* level decoder not initialised (V2, zero length)    */
   PQG_ERR_GZIP = -15,         /* gzip: invalid header / data / checksum (compress.go:63-76) */
   PQG_ERR_ZSTD = -16,         /* zstd: invalid frame / block / checksum             */
+  PQG_ERR_LZ4 = -17,          /* lz4_raw: a block liblz4's LZ4_decompress_safe rejects */
   PQG_ERR_FIXED_LEN = -14,    /* DELTA_BYTE_ARRAY on FIXED_LEN_BYTE_ARRAY: a value  */
                               /* whose length is not type_length (the reference     */
                               /* returns it; the fixed-width output cannot hold it) */
@@ -258,7 +260,10 @@ int pqg_decode_page(pqg_ctx* ctx, const pqg_page_job* job, pqg_chunk_result* res
  * (libzstd's ZSTD_decompress over the whole block: any number of frames and
  * skippable frames, content checksums verified, no dictionaries; an invalid
  * frame / block / checksum, a content size that differs from the decoded one
- * or trailing bytes -> PQG_ERR_ZSTD) or UNCOMPRESSED (a copy).  *out_len is the decoded length; PQG_ERR_CAPACITY
+ * or trailing bytes -> PQG_ERR_ZSTD), LZ4_RAW (one bare LZ4 block, as liblz4's
+ * LZ4_decompress_safe decodes it into a buffer of 255 * n + 64 bytes, which no
+ * block can fill; a block it rejects, n == 0 among them -> PQG_ERR_LZ4) or
+ * UNCOMPRESSED (a copy).  *out_len is the decoded length; PQG_ERR_CAPACITY
  * when it exceeds `cap` (nothing written). */
 int pqg_block_decompress(pqg_ctx* ctx, int codec, const uint8_t* src, int64_t n, uint8_t* dst, int64_t cap,
                          int64_t* out_len);

@@ -38,6 +38,7 @@ enum : int32_t {
   kFIXED_LEN = -14,  // DELTA_BYTE_ARRAY on FLBA: a value of another length than type_length
   kGZIP = -15,       // gzip: invalid header, DEFLATE data or checksum
   kZSTD = -16,       // zstd: invalid frame, block or checksum
+  kLZ4 = -17,        // lz4: a block LZ4_decompress_safe rejects
   kCAPACITY = -20,
   kCOMPLEX = -30,   // internal: header needs the serial walk (deep thrift nesting)
 };
@@ -86,11 +87,11 @@ struct PageDev {
   // compressed segments, and the serial-fallback flag (non-zero: k_snappy
   // decodes the page as one block)
   int32_t sn_hdr, sn_nsub, sn_sub_base, sn_nseg, sn_seg_base, sn_fallback;
-  int64_t gz_len;          // K2g / K2z (pqg_inflate.hip, pqg_zstd.hip), bare blocks: decoded bytes
+  int64_t gz_len;          // K2g / K2z / K2l (pqg_inflate.hip, pqg_zstd.hip, pqg_lz4.hip), bare blocks: decoded bytes
 };
 constexpr int32_t kPageBareBlock = 1 << 4;  // PageDev.flags: a pqg_block_decompress block (no page around it)
 constexpr int32_t kPageInflateRedo = 1 << 6;  // PageDev.flags: a GZIP page for k_inflate's 32 KiB ring (k_inflate_s left it)
-constexpr int32_t kCodecSnappy = 1, kCodecGzip = 2, kCodecZstd = 6;  // parquet CompressionCodec numbers
+constexpr int32_t kCodecSnappy = 1, kCodecGzip = 2, kCodecZstd = 6, kCodecLz4Raw = 7;  // parquet CompressionCodec numbers
 
 // K2 snappy sub-block: the output [j * kSnapSub, (j + 1) * kSnapSub) of one
 // compressed block, decoded by one wave from a chain tag at or before its
@@ -333,8 +334,9 @@ constexpr int kQueueLevGen = 15;  // k_page_levels when k_page_levels_w1 takes t
 constexpr int kQueueDictBig = 16; // k_dict4_big: run-table pages of dictionaries past 4096 entries
 constexpr int kQueueInflateRedo = 17;  // k_inflate (32 KiB ring) over the pages k_inflate_s left
 constexpr int kQueueZstd = 18;  // ZSTD pages (k_zstd)
-// queue regions zeroed per launch: 0-8, the stage flags (9), 10-18
-constexpr int kQueueSlots = 19;
+constexpr int kQueueLz4 = 19;   // LZ4_RAW pages (k_lz4)
+// queue regions zeroed per launch: 0-8, the stage flags (9), 10-19
+constexpr int kQueueSlots = 20;
 constexpr int kPresentBigDict = 8;  // stage flag (kModePresentOff + 8): a page for k_dict4_big
 
 // Scan tiles of the speculative page-header search.

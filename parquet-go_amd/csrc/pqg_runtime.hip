@@ -18,6 +18,7 @@
 
 #include "../../include/pqgpu.h"
 #include "pqg_common.h"
+#include "pqg_lz4.h"
 #include "pqg_zstd.h"
 
 namespace pqg {
@@ -51,6 +52,9 @@ __global__ void k_inflate(JobDev* jobs, PageDev* pages, const int* list, const i
                           uint8_t* scratch, int mode);
 __global__ void k_zstd(JobDev* jobs, PageDev* pages, const int* list, const int* total, int* queue, uint8_t* scratch,
                        uint8_t* wspace);
+__global__ void k_lz4(JobDev* jobs, PageDev* pages, const int* list, const int* total, int* queue, uint8_t* scratch);
+__global__ void k_lz4_batch(JobDev* jobs, PageDev* pages, const int* list, const int* total, int* queue,
+                            uint8_t* scratch);
 __global__ void k_inflate_s(JobDev* jobs, PageDev* pages, const int* list, const int* total, int* queue,
                             uint8_t* scratch);
 __global__ void k_snap_plan(const JobDev* jobs, PageDev* pages, const int* list, const int* total, int* ctr,
@@ -180,6 +184,12 @@ int value_width_of(const pqg_column_desc& c) {
 
 }  // namespace
 
+// Which of pqg_lz4.hip's two decoders the runtime launches unless the environment says otherwise: 1, step B
+// (k_lz4_batch), the faster one on both shapes measured; 0: step A (k_lz4).
+#ifndef PQG_LZ4_BATCH
+#define PQG_LZ4_BATCH 1
+#endif
+
 struct pqg_ctx;
 static unsigned zstd_grid(const pqg_ctx* c);
 
@@ -200,6 +210,9 @@ struct pqg_ctx {
   int snappy_per_cu = 2;  // resident k_snappy waves per CU (LDS-bound: the output history ring)
   int inflate_per_cu = 8; // resident k_inflate_s waves per CU (LDS / VGPR bound), from the occupancy query
   int zstd_per_cu = 8;    // resident k_zstd waves per CU (LDS-bound: its tables), from the occupancy query
+  int lz4_per_cu = 8;     // resident k_lz4 / k_lz4_batch waves per CU, from the occupancy query
+  bool lz4_batch = PQG_LZ4_BATCH;  // LZ4_RAW pages by k_lz4_batch (step B), not k_lz4 (step A); PQG_LZ4_BATCH=0/1 in the
+                                   // environment overrides the build's choice for a context (tests, tools/lz4_probe.py)
   DevBuf zstd_ws;         // k_zstd: a literal workspace (zstd::kWsBytes) per wave of its grid
   DevBuf jobs, pages, list, counters, def_arena, rep_arena, value_arena, scratch;
   DevBuf tile_job;  // K1: tile -> job
@@ -267,6 +280,7 @@ const char* pqg_status_string(int s) {
     case PQG_ERR_FIXED_LEN: return "bytearray/delta: value length is not the fixed length";
     case PQG_ERR_GZIP: return "gzip: invalid data";
     case PQG_ERR_ZSTD: return "zstd: invalid frame / block / checksum";
+    case PQG_ERR_LZ4: return "lz4: invalid block";
     case PQG_ERR_CAPACITY: return "capacity";
     case PQG_ERR_INVALID_ARG: return "invalid argument";
     case PQG_ERR_HIP: return "HIP runtime error";
@@ -320,6 +334,12 @@ int pqg_ctx_create(int device, pqg_ctx** out) {
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void*>(&k_zstd), 64, 0) ==
           hipSuccess && occ > 0)
     c->zstd_per_cu = occ;
+  occ = 0;
+  if (const char* e = getenv("PQG_LZ4_BATCH")) c->lz4_batch = atoi(e) != 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(
+          &occ, c->lz4_batch ? reinterpret_cast<const void*>(&k_lz4_batch) : reinterpret_cast<const void*>(&k_lz4), 64, 0) == hipSuccess &&
+      occ > 0)
+    c->lz4_per_cu = occ;
   // counters: ctr[0..1023] + the kQShards-sharded work queues and the per-stage flags
   if (c->counters.grow(sizeof(int) * (size_t)(1024 + kQueueSlots * kQueueInts))) {
     pqg_ctx_destroy(c);
@@ -600,11 +620,12 @@ static int launch_pipeline(pqg_ctx* c) {
   hipLaunchKernelGGL(k_page_list, page_grid, dim3(1024), 0, s, jobs, pages, n, list,
                      (int)std::min<int64_t>(c->list_cap, INT32_MAX), ctr, ctr + 8);
   if (c->timed) hipEventRecord(c->ev[2], s);
-  bool any_snappy = false, any_gzip = false, any_zstd = false;
+  bool any_snappy = false, any_gzip = false, any_zstd = false, any_lz4 = false;
   for (int i = 0; i < n; i++) {
     any_snappy |= c->cur[(size_t)i].col.codec == PQG_CODEC_SNAPPY;
     any_gzip |= c->cur[(size_t)i].col.codec == PQG_CODEC_GZIP;
     any_zstd |= c->cur[(size_t)i].col.codec == PQG_CODEC_ZSTD;
+    any_lz4 |= c->cur[(size_t)i].col.codec == PQG_CODEC_LZ4_RAW;
   }
   if (any_snappy) {
     const SnapTables T{(SnapSub*)c->sn_subs.p, (int)std::min<int64_t>(c->sn_sub_cap, INT32_MAX), (int*)c->sn_segpage.p,
@@ -620,6 +641,9 @@ static int launch_pipeline(pqg_ctx* c) {
   if (any_zstd)  // one wave per ZSTD page (pqg_zstd.hip), each with its literal workspace (plan_batch)
     hipLaunchKernelGGL(k_zstd, dim3(zstd_grid(c)), dim3(64), 0, s, jobs, pages, list, ctr, Q(kQueueZstd), scratch,
                        (uint8_t*)c->zstd_ws.p);
+  if (any_lz4)  // one wave per LZ4_RAW page (pqg_lz4.hip); no workspace
+    hipLaunchKernelGGL(c->lz4_batch ? k_lz4_batch : k_lz4, dim3(qgrid((int64_t)c->num_cus * c->lz4_per_cu)), dim3(64), 0, s, jobs, pages, list, ctr,
+                       Q(kQueueLz4), scratch);
   if (c->timed) hipEventRecord(c->ev[3], s);
   HStream* streams = (HStream*)c->streams.p;
   RunEnt* runs = (RunEnt*)c->runs.p;
@@ -1039,16 +1063,16 @@ static int block_inflate(pqg_ctx* c, const uint8_t* src, int64_t n, uint8_t* dst
   return PQG_OK;
 }
 
-// zstd's ZSTD_decompress over one host block.  The output buffer is sized
-// before the decode from the block itself (zstd::decoded_bound: the frames'
-// content sizes, or per block its size / the 128 KiB block maximum), so one
-// pass decodes it whatever `cap` is; k_zstd never stores past that buffer.
-static int block_zstd(pqg_ctx* c, const uint8_t* src, int64_t n, uint8_t* dst, int64_t cap, int64_t* out_len) {
+// One bare block as the only page of a job, for the decoders that take a page per wave (k_zstd,
+// k_lz4): uploads src[0..n), sets up the job, a kPageBareBlock page with room for `store` decoded
+// bytes in blk_dst, its list and queue, has `launch` start the kernel on them (jobs, pages, list,
+// total, queue, scratch), and returns the page record as the kernel left it (read_status, gz_len).
+extern "C++" {
+template <class Launch>
+static int block_by_page_wave(pqg_ctx* c, int codec, const uint8_t* src, int64_t n, int64_t store, PageDev* out,
+                              Launch launch) {
   hipSetDevice(c->device);
-  bool exact = false;
-  const int64_t store = zstd::decoded_bound(src, n, &exact);
-  if (store > INT32_MAX) return PQG_ERR_UNSUPPORTED;  // one block of >= 2 GiB
-  if (c->blk_src.grow((size_t)n + 64) || c->blk_dst.grow((size_t)store + 64) || c->zstd_ws.grow((size_t)zstd_grid(c) * zstd::kWsBytes) ||
+  if (c->blk_src.grow((size_t)n + 64) || c->blk_dst.grow((size_t)store + 64) ||
       c->blk_meta.grow(sizeof(JobDev) + sizeof(PageDev) + (4 + 2 * kQueueInts) * sizeof(int)))
     return PQG_ERR_HIP;
   JobDev jd;
@@ -1056,7 +1080,7 @@ static int block_zstd(pqg_ctx* c, const uint8_t* src, int64_t n, uint8_t* dst, i
   jd.data = (const uint8_t*)c->blk_src.p;
   jd.data_len = n;
   jd.tcs = n;
-  jd.codec = PQG_CODEC_ZSTD;
+  jd.codec = codec;
   jd.scratch_cap = store + 16;
   PageDev pd;
   memset(&pd, 0, sizeof(pd));
@@ -1064,6 +1088,7 @@ static int block_zstd(pqg_ctx* c, const uint8_t* src, int64_t n, uint8_t* dst, i
   pd.flags = kPageBareBlock;
   pd.csize = (int32_t)n;
   pd.usize = (int32_t)store;
+  pd.gz_len = -1;
   pd.read_status = kOK;
   uint8_t* meta = (uint8_t*)c->blk_meta.p;
   JobDev* djob = (JobDev*)meta;
@@ -1076,19 +1101,67 @@ static int block_zstd(pqg_ctx* c, const uint8_t* src, int64_t n, uint8_t* dst, i
       hipMemcpyAsync(ints, hi, sizeof(hi), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
       hipMemsetAsync(ints + 4, 0, sizeof(int) * kQueueInts, c->stream) != hipSuccess)
     return PQG_ERR_HIP;
-  hipLaunchKernelGGL(k_zstd, dim3(qgrid(1)), dim3(64), 0, c->stream, djob, dpage, ints, ints + 1, ints + 4,
-                     (uint8_t*)c->blk_dst.p, (uint8_t*)c->zstd_ws.p);
+  launch(djob, dpage, ints, ints + 1, ints + 4, (uint8_t*)c->blk_dst.p);
   if (hipGetLastError() != hipSuccess) return PQG_ERR_HIP;
-  if (hipMemcpyAsync(&pd, dpage, sizeof(PageDev), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+  if (hipMemcpyAsync(out, dpage, sizeof(PageDev), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
       hipStreamSynchronize(c->stream) != hipSuccess)
     return PQG_ERR_HIP;
+  return PQG_OK;
+}
+}  // extern "C++"
+
+// the decoded bytes of such a block, from blk_dst to the caller
+static int block_copy_back(pqg_ctx* c, uint8_t* dst, int64_t len) {
+  if (len && (hipMemcpyAsync(dst, c->blk_dst.p, (size_t)len, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+              hipStreamSynchronize(c->stream) != hipSuccess))
+    return PQG_ERR_HIP;
+  return PQG_OK;
+}
+
+// zstd's ZSTD_decompress over one host block.  The output buffer is sized
+// before the decode from the block itself (zstd::decoded_bound: the frames'
+// content sizes, or per block its size / the 128 KiB block maximum), so one
+// pass decodes it whatever `cap` is; k_zstd never stores past that buffer.
+static int block_zstd(pqg_ctx* c, const uint8_t* src, int64_t n, uint8_t* dst, int64_t cap, int64_t* out_len) {
+  bool exact = false;
+  const int64_t store = zstd::decoded_bound(src, n, &exact);
+  if (store > INT32_MAX) return PQG_ERR_UNSUPPORTED;  // one block of >= 2 GiB
+  hipSetDevice(c->device);
+  if (c->zstd_ws.grow((size_t)zstd_grid(c) * zstd::kWsBytes)) return PQG_ERR_HIP;
+  PageDev pd;
+  const int e = block_by_page_wave(c, PQG_CODEC_ZSTD, src, n, store, &pd,
+                                   [&](JobDev* jobs, PageDev* pages, int* list, int* total, int* queue, uint8_t* scratch) {
+                                     hipLaunchKernelGGL(k_zstd, dim3(qgrid(1)), dim3(64), 0, c->stream, jobs, pages, list,
+                                                        total, queue, scratch, (uint8_t*)c->zstd_ws.p);
+                                   });
+  if (e) return e;
   if (pd.read_status != kOK) return pd.read_status;
   *out_len = pd.gz_len;
   if (pd.gz_len > cap) return PQG_ERR_CAPACITY;
-  if (pd.gz_len && (hipMemcpyAsync(dst, c->blk_dst.p, (size_t)pd.gz_len, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-                    hipStreamSynchronize(c->stream) != hipSuccess))
-    return PQG_ERR_HIP;
-  return PQG_OK;
+  return block_copy_back(c, dst, pd.gz_len);
+}
+
+// LZ4_decompress_safe over one host block, into a buffer no block can fill.
+// The host walks the sequences first (lz4::decoded_length: the exact decoded
+// length, or the verdict on a malformed block), so the device buffer is sized
+// once, a too small `cap` is answered without a launch, and the kernel never
+// stores past the walked length.
+static int block_lz4(pqg_ctx* c, const uint8_t* src, int64_t n, uint8_t* dst, int64_t cap, int64_t* out_len) {
+  const int64_t len = lz4::decoded_length(src, n);
+  if (len < 0) return PQG_ERR_LZ4;
+  *out_len = len;
+  if (len > cap) return PQG_ERR_CAPACITY;
+  if (len > INT32_MAX) return PQG_ERR_UNSUPPORTED;  // one block of >= 2 GiB
+  PageDev pd;
+  const int e = block_by_page_wave(c, PQG_CODEC_LZ4_RAW, src, n, len, &pd,
+                                   [&](JobDev* jobs, PageDev* pages, int* list, int* total, int* queue, uint8_t* scratch) {
+                                     hipLaunchKernelGGL(c->lz4_batch ? k_lz4_batch : k_lz4, dim3(qgrid(1)), dim3(64), 0,
+                                                        c->stream, jobs, pages, list, total, queue, scratch);
+                                   });
+  if (e) return e;
+  if (pd.read_status != kOK) return pd.read_status;
+  if (pd.gz_len != len) return PQG_ERR_LZ4;  // the kernel and the host walk are one decoder: never
+  return block_copy_back(c, dst, len);
 }
 
 int pqg_block_decompress(pqg_ctx* c, int codec, const uint8_t* src, int64_t n, uint8_t* dst, int64_t cap,
@@ -1103,6 +1176,7 @@ int pqg_block_decompress(pqg_ctx* c, int codec, const uint8_t* src, int64_t n, u
   }
   if (codec == PQG_CODEC_GZIP) return block_inflate(c, src, n, dst, cap, out_len);
   if (codec == PQG_CODEC_ZSTD) return block_zstd(c, src, n, dst, cap, out_len);
+  if (codec == PQG_CODEC_LZ4_RAW) return block_lz4(c, src, n, dst, cap, out_len);
   if (codec != PQG_CODEC_SNAPPY) return PQG_ERR_UNSUPPORTED;
   // decodedLen (decode.go:32-43): the varint header, on the host to size the output
   uint64_t v = 0;

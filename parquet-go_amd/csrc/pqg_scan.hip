@@ -42,9 +42,9 @@ struct WinSrc {
 //                     both paths share classify_page.
 // ============================================================================
 
-// codecs with a decompression stage (K2 snappy, K2g gzip, K2z zstd)
+// codecs with a decompression stage (K2 snappy, K2g gzip, K2z zstd, K2l lz4_raw)
 __device__ __forceinline__ bool codec_supported(int codec) {
-  return codec == kCodecSnappy || codec == kCodecGzip || codec == kCodecZstd;
+  return codec == kCodecSnappy || codec == kCodecGzip || codec == kCodecZstd || codec == kCodecLz4Raw;
 }
 
 // Read-phase classification of one parsed header (readPages :216-272 with

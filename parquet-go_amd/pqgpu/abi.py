@@ -16,6 +16,7 @@ ENC_DELTA_BYTE_ARRAY = 7
 ENC_RLE_DICTIONARY = 8
 CODEC_UNCOMPRESSED, CODEC_SNAPPY, CODEC_GZIP = 0, 1, 2
 CODEC_ZSTD = 6
+CODEC_LZ4_RAW = 7
 PAGE_DATA, PAGE_INDEX, PAGE_DICTIONARY, PAGE_DATA_V2 = 0, 1, 2, 3
 
 STATUS = {
@@ -36,6 +37,7 @@ STATUS = {
     -14: "FIXED_LEN",
     -15: "GZIP",
     -16: "ZSTD",
+    -17: "LZ4",
     -20: "CAPACITY",
     -21: "INVALID_ARG",
     -22: "HIP",
