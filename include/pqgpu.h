@@ -54,7 +54,15 @@ enum {
   PQG_ENC_DELTA_BINARY_PACKED = 5,
   PQG_ENC_DELTA_LENGTH_BYTE_ARRAY = 6,
   PQG_ENC_DELTA_BYTE_ARRAY = 7,
-  PQG_ENC_RLE_DICTIONARY = 8
+  PQG_ENC_RLE_DICTIONARY = 8,
+  /* BYTE_STREAM_SPLIT (beyond the reference, which has no such decoder): data pages of
+   * INT32 / INT64 / FLOAT / DOUBLE and of FIXED_LEN_BYTE_ARRAY with type_length >= 1;
+   * on BOOLEAN / INT96 / BYTE_ARRAY / type_length < 1 the page's read error is
+   * PQG_ERR_UNSUPPORTED.  A page of nn non-null values of w bytes holds w streams of nn
+   * bytes, so its value bytes must be exactly nn * w: fewer is PQG_ERR_EOF (as for
+   * PLAIN), more is PQG_ERR_SIZE (unlike PLAIN, which ignores trailing bytes: with
+   * extra bytes the streams' stride is ambiguous); both are decode errors of the page. */
+  PQG_ENC_BYTE_STREAM_SPLIT = 9
 };
 enum {
   PQG_CODEC_UNCOMPRESSED = 0,
@@ -81,7 +89,8 @@ enum {
   PQG_ERR_EOF = -1,           /* io.EOF / io.ErrUnexpectedEOF inside a stream       */
   PQG_ERR_THRIFT = -2,        /* PageHeader thrift-compact decode failed            */
   PQG_ERR_PAGE_HEADER = -3,   /* missing sub-header, negative count/size            */
-  PQG_ERR_SIZE = -4,          /* block shorter than compressed size / size mismatch */
+  PQG_ERR_SIZE = -4,          /* block shorter than compressed size / size mismatch; */
+                              /* BYTE_STREAM_SPLIT: more value bytes than nn * w     */
   PQG_ERR_SNAPPY = -5,        /* snappy: corrupt input                              */
   PQG_ERR_RLE = -6,           /* hybrid: empty run, RLE value too large, bad varint */
   PQG_ERR_DICT_INDEX = -7,    /* dict: invalid index                                */

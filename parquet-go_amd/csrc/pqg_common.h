@@ -73,7 +73,8 @@ struct PageDev {
   int32_t flags;
   int32_t dict_width;      // RLE_DICTIONARY: index bit width byte
   int32_t hs_rep, hs_def, hs_val;  // hybrid streams of the page (HStream index, -1: none)
-  int32_t vmode;           // values stage of the page: 1 4-byte dictionary, 3 DELTA_BINARY_PACKED, 0 other fixed width, 2 variable, -1 none
+  int32_t vmode;           // values stage of the page: 1 4-byte dictionary, 3 DELTA_BINARY_PACKED, 0 other fixed width, 2 variable,
+                           // 5 BYTE_STREAM_SPLIT (kModeBss), -1 none
   int64_t run_off, blk_off;  // the page's run-table / block-index region (job-relative, k_page_list)
   // variable-length values (BYTE_ARRAY, FLBA of length 0): chars of the page
   // and their offset in the chunk's chars (exclusive scan over the pages)
@@ -320,9 +321,12 @@ constexpr int kQShards = 8;
 constexpr int kQStride = 32;
 constexpr int kQueueInts = kQShards * kQStride;
 // ints after the counters base (ctr[0] = page-list total): one flag per values
-// stage (PageDev.vmode 0..3), set by k_page_levels when a page of that stage
+// stage (PageDev.vmode 0..3 and kModeBss), set by k_page_levels when a page of that stage
 // exists, so an empty stage's kernel exits at once instead of walking the list
 constexpr int kModePresentOff = 1024 + 9 * kQueueInts;
+// BYTE_STREAM_SPLIT pages (k_bss, pqg_bss.hip): their values stage and its flag (4 is the
+// DELTA_*_BYTE_ARRAY flag, 8 kPresentBigDict)
+constexpr int kModeBss = 5;
 // the serial snappy pass (k_snappy after the split decode) pulls its own queue
 constexpr int kQueueSnapSerial = 10;
 // DELTA_LENGTH_BYTE_ARRAY / DELTA_BYTE_ARRAY lengths (k_str_delta) and values (k_str_dba)
@@ -335,8 +339,9 @@ constexpr int kQueueDictBig = 16; // k_dict4_big: run-table pages of dictionarie
 constexpr int kQueueInflateRedo = 17;  // k_inflate (32 KiB ring) over the pages k_inflate_s left
 constexpr int kQueueZstd = 18;  // ZSTD pages (k_zstd)
 constexpr int kQueueLz4 = 19;   // LZ4_RAW pages (k_lz4)
-// queue regions zeroed per launch: 0-8, the stage flags (9), 10-19
-constexpr int kQueueSlots = 20;
+constexpr int kQueueBss = 20;   // parts of BYTE_STREAM_SPLIT pages (k_bss)
+// queue regions zeroed per launch: 0-8, the stage flags (9), 10-20
+constexpr int kQueueSlots = 21;
 constexpr int kPresentBigDict = 8;  // stage flag (kModePresentOff + 8): a page for k_dict4_big
 
 // Scan tiles of the speculative page-header search.

@@ -78,8 +78,10 @@ __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
 
 __device__ __forceinline__ int bits_len(uint32_t v) { return v ? 32 - __builtin_clz(v) : 0; }
 
-// getValuesDecoder chunk_reader.go:143-196
+// getValuesDecoder chunk_reader.go:143-196; BYTE_STREAM_SPLIT (9, beyond the reference: k_bss)
+// on INT32 / INT64 / FLOAT / DOUBLE and on FLBA of type_length >= 1
 __device__ __forceinline__ int values_supported(int type, int type_length, int enc) {
+  if (enc == 9) return type == 1 || type == 2 || type == 4 || type == 5 || (type == 7 && type_length >= 1);
   switch (type) {
     case 0: return enc == 0 || enc == 3 || enc == 8;
     case 6: return enc == 0 || enc == 8 || enc == 6 || enc == 7;  // + DELTA_LENGTH_BYTE_ARRAY / DELTA_BYTE_ARRAY

@@ -755,7 +755,8 @@ __device__ __forceinline__ PageStreams page_setup(const JobDev& job, const PageD
   gcu8 val = block + vpos;
   r.val = val;
   r.val_n = vn;
-  r.vmode = job.value_width == 0 || (pg.encoding == 7 && job.type == 7) ? 2
+  r.vmode = pg.encoding == 9 && job.value_width > 0                    ? kModeBss
+            : job.value_width == 0 || (pg.encoding == 7 && job.type == 7) ? 2
             : (pg.encoding == 8 && job.value_width == 4)                ? 1
             : pg.encoding == 5                                          ? 3
                                                                         : 0;
@@ -781,7 +782,8 @@ __device__ __forceinline__ PageStreams page_setup(const JobDev& job, const PageD
     }
     // value-stage page lists: 4-byte dictionary pages (the hot path, a kernel
     // of its own), variable-length values (pqg_strings.hip) and everything else
-    // (DELTA_BYTE_ARRAY on FLBA: the strings stage, values of type_length bytes)
+    // (DELTA_BYTE_ARRAY on FLBA: the strings stage, values of type_length bytes);
+    // BYTE_STREAM_SPLIT pages: k_bss
     const int vm = r.vmode;
     P.vmode = vm;
     int* present = const_cast<int*>(total) + kModePresentOff;

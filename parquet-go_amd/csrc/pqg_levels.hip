@@ -770,7 +770,7 @@ __device__ __forceinline__ int64_t part_count(const PageDev& pg, const HStream* 
   const int enc = pg.encoding;
   if (pg.vmode == 2 && enc != 0 && enc != 8) return 0;  // DELTA_(LENGTH_)BYTE_ARRAY: one part
   const int64_t nn = pg.not_null;
-  if (enc == 0 || nn <= kSplitMin) return nn;            // PLAIN: value ranges; small pages: one part
+  if (enc == 0 || enc == 9 || nn <= kSplitMin) return nn;  // PLAIN, BYTE_STREAM_SPLIT: value ranges; small pages: one part
   if ((enc == 8 || enc == 3) && pg.hs_val >= 0) {         // hybrid value stream: block ranges
     const HStream& S = streams[pg.hs_val];
     *hyb = true;

@@ -84,6 +84,8 @@ __global__ void k_nn_scan(JobDev* jobs, PageDev* pages, uint8_t* scratch, const 
 template <int Mode>
 __global__ void k_values(JobDev* jobs, PageDev* pages, const PartRec* parts, const int* total, int* queue,
                          uint8_t* value_arena, const HStream* streams, const RunEnt* runs, const BlockDesc* blks);
+__global__ void k_bss(JobDev* jobs, PageDev* pages, const PartRec* parts, const int* total, int* queue,
+                      uint8_t* value_arena);
 __global__ void k_dict_plan(JobDev* jobs, PageDev* pages, const PartRec* parts, const int* total,
                             uint8_t* value_arena, const HStream* streams, const RunEnt* runs, const BlockDesc* blks,
                             VRec* recs);
@@ -113,6 +115,7 @@ int prof_read_strings(unsigned long long* out);
 int prof_read_snappy(unsigned long long* out);
 int prof_read_dict(unsigned long long* out);
 int prof_read_inflate(unsigned long long* out);
+int prof_read_bss(unsigned long long* out);
 }  // namespace pqg
 #endif
 
@@ -578,7 +581,8 @@ static int launch_pipeline(pqg_ctx* c) {
   // work queues (sharded over the XCDs, see queue_pull): 0 snappy, 1 levels,
   // 2 values<0>, 3 values<1>, 4 str_count, 5 str_plain, 6 str_copy, 7 the
   // candidate list heads of k_page_cands, 8 values<3> (DELTA_BINARY_PACKED); then
-  // the per-stage page flags (kModePresentOff)
+  // the per-stage page flags (kModePresentOff) and the queues named in pqg_common.h
+  // (kQueueBss: k_bss)
   auto Q = [&](int k) { return ctr + 1024 + k * kQueueInts; };
   uint8_t* scratch = (uint8_t*)c->scratch.p;
   // page-queue kernels: one wave per page; enough waves per SIMD to hide the
@@ -719,6 +723,9 @@ static int launch_pipeline(pqg_ctx* c) {
                        (uint8_t*)c->value_arena.p, streams, runs, blks);
     hipLaunchKernelGGL(k_values<3>, dim3(qgrid(waves)), dim3(64), 0, s, jobs, pages, parts, ctr, Q(8),
                        (uint8_t*)c->value_arena.p, streams, runs, blks);
+    // BYTE_STREAM_SPLIT pages (pqg_bss.hip): part of the values stage's time (ev[7] .. ev[8])
+    hipLaunchKernelGGL(k_bss, dim3(qgrid(waves)), dim3(64), 0, s, jobs, pages, parts, ctr, Q(kQueueBss),
+                       (uint8_t*)c->value_arena.p);
   }
   if (c->timed) hipEventRecord(c->ev[8], s);
   if (c->any_var) {
@@ -1297,24 +1304,26 @@ int pqg_get_pages(pqg_ctx* c, int job, pqg_page_info* out, int cap) {
 
 // Diagnostic builds (-DPQG_PROFILE): in-kernel phase cycle counters of the
 // values (slots 0-31), levels (slots 32-63), strings (64-95), snappy
-// (96-127) and dictionary (128-159) translation units; read + reset.
+// (96-127), dictionary (128-159), inflate (160-191) and BYTE_STREAM_SPLIT
+// (192-223, pqg_bss.hip) translation units; read + reset.
 int pqg_debug_counters(pqg_ctx* c, uint64_t* out, int cap) {
   if (!c || !out) return PQG_ERR_INVALID_ARG;
 #ifdef PQG_PROFILE
   hipSetDevice(c->device);
   hipStreamSynchronize(c->stream);
-  unsigned long long a[64], b[64], c3[64], d4[64], e5[64], f6[64];
+  unsigned long long a[64], b[64], c3[64], d4[64], e5[64], f6[64], g7[64];
   if (pqg::prof_read_values(a) || pqg::prof_read_levels(b) || pqg::prof_read_strings(c3) ||
-      pqg::prof_read_snappy(d4) || pqg::prof_read_dict(e5) || pqg::prof_read_inflate(f6))
+      pqg::prof_read_snappy(d4) || pqg::prof_read_dict(e5) || pqg::prof_read_inflate(f6) || pqg::prof_read_bss(g7))
     return PQG_ERR_HIP;
   int k = 0;
-  for (; k < 192 && k < cap; k++)
+  for (; k < 224 && k < cap; k++)
     out[k] = k < 32    ? a[k]
              : k < 64  ? b[k - 32]
              : k < 96  ? c3[k - 64]
              : k < 128 ? d4[k - 96]
              : k < 160 ? e5[k - 128]
-                       : f6[k - 160];
+             : k < 192 ? f6[k - 160]
+                       : g7[k - 192];
   return k;
 #else
   return 0;

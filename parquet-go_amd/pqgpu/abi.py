@@ -14,6 +14,7 @@ ENC_DELTA_BINARY_PACKED = 5
 ENC_DELTA_LENGTH_BYTE_ARRAY = 6
 ENC_DELTA_BYTE_ARRAY = 7
 ENC_RLE_DICTIONARY = 8
+ENC_BYTE_STREAM_SPLIT = 9
 CODEC_UNCOMPRESSED, CODEC_SNAPPY, CODEC_GZIP = 0, 1, 2
 CODEC_ZSTD = 6
 CODEC_LZ4_RAW = 7
