@@ -103,6 +103,8 @@ enum {
   PQG_ERR_GZIP = -15,         /* gzip: invalid header / data / checksum (compress.go:63-76) */
   PQG_ERR_ZSTD = -16,         /* zstd: invalid frame / block / checksum             */
   PQG_ERR_LZ4 = -17,          /* lz4_raw: a block liblz4's LZ4_decompress_safe rejects */
+  PQG_ERR_CRC = -18,          /* PageHeader.crc does not match the page's bytes; a   */
+                              /* read-phase error, only with pqg_set_verify_crc on   */
   PQG_ERR_FIXED_LEN = -14,    /* DELTA_BYTE_ARRAY on FIXED_LEN_BYTE_ARRAY: a value  */
                               /* whose length is not type_length (the reference     */
                               /* returns it; the fixed-width output cannot hold it) */
@@ -301,6 +303,45 @@ int pqg_last_timings(pqg_ctx* ctx, float* out, int cap);
  * events are instrumentation: each costs a few microseconds of stream time,
  * which matters for small batches. */
 int pqg_set_timing(pqg_ctx* ctx, int on);
+
+/* ---- page checksums (PageHeader.crc, field 4) -----------------------------
+ * Off by default (PQG_VERIFY_CRC=0/1 in the environment sets a new context's
+ * value); `on` holds for later decodes on the ctx, pqg_decode_page included.
+ * With it on, every page whose header holds field 4 as an i32 (the last one
+ * if it appears twice) and whose own read phase is OK is checked before any
+ * decoder reads it: CRC-32 as in zlib / gzip over the compressed_page_size
+ * bytes that follow the thrift header, as stored (V2: levels and values
+ * together; dictionary pages the same), compared as uint32.  A mismatch is a
+ * read-phase error of that page, PQG_ERR_CRC: it ranks in
+ * pqg_chunk_result.status / error_page before any decode error, the first
+ * failing page in file order wins, and no decoder reads the page.  Pages
+ * without the field decode as with verification off. */
+int pqg_set_verify_crc(pqg_ctx* ctx, int on);
+
+typedef struct pqg_page_crc {
+  uint32_t stored;    /* PageHeader.crc as uint32 (0 when absent)                */
+  uint32_t computed;  /* CRC-32 of the page's bytes (states 1 and 2)             */
+  int32_t state;      /* PQG_CRC_*                                               */
+  int32_t reserved;
+} pqg_page_crc;
+enum {
+  PQG_CRC_NONE = 0,         /* the header has no crc field                       */
+  PQG_CRC_VERIFIED = 1,
+  PQG_CRC_MISMATCH = 2,
+  PQG_CRC_NOT_CHECKED = 3,  /* verification off, or a read error of the page itself */
+};
+/* After pqg_sync: the checksum record of each page pqg_get_pages reports for
+ * job `job`, in the same order.  Returns entries written or a negative status. */
+int pqg_get_page_crcs(pqg_ctx* ctx, int job, pqg_page_crc* out, int cap);
+
+/* zlib's crc32 of the device buffer [dev, dev + n), by the kernel that checks
+ * the pages (n == 0 -> 0).  Only 16-byte granules that hold a byte of the
+ * range are loaded.  Synchronises the ctx stream. */
+int pqg_crc32(pqg_ctx* ctx, const uint8_t* dev, int64_t n, uint32_t* out);
+
+/* Device time in ms of the checksum kernels of the last decode (0 when it
+ * ran none: verification off, or stage timing off). */
+int pqg_last_crc_ms(pqg_ctx* ctx, float* ms);
 
 /* Optional: run `iters` back-to-back decodes of the same jobs on the ctx
  * stream and return the device time in ms (used by bench.py).  */

@@ -39,6 +39,7 @@ enum : int32_t {
   kGZIP = -15,       // gzip: invalid header, DEFLATE data or checksum
   kZSTD = -16,       // zstd: invalid frame, block or checksum
   kLZ4 = -17,        // lz4: a block LZ4_decompress_safe rejects
+  kCRC = -18,        // PageHeader.crc does not match the page's bytes (k_crc_fin; only with verification on)
   kCAPACITY = -20,
   kCOMPLEX = -30,   // internal: header needs the serial walk (deep thrift nesting)
 };
@@ -340,8 +341,12 @@ constexpr int kQueueInflateRedo = 17;  // k_inflate (32 KiB ring) over the pages
 constexpr int kQueueZstd = 18;  // ZSTD pages (k_zstd)
 constexpr int kQueueLz4 = 19;   // LZ4_RAW pages (k_lz4)
 constexpr int kQueueBss = 20;   // parts of BYTE_STREAM_SPLIT pages (k_bss)
-// queue regions zeroed per launch: 0-8, the stage flags (9), 10-20
-constexpr int kQueueSlots = 21;
+// tiles of the pages whose PageHeader.crc is verified (k_page_crc, pqg_crc.hip); int kCrcTileCtr of
+// the region (between two queue heads, zeroed with them) counts the tile records k_crc_plan reserved
+constexpr int kQueueCrc = 21;
+constexpr int kCrcTileCtr = 1;
+// queue regions zeroed per launch: 0-8, the stage flags (9), 10-21
+constexpr int kQueueSlots = 22;
 constexpr int kPresentBigDict = 8;  // stage flag (kModePresentOff + 8): a page for k_dict4_big
 
 // Scan tiles of the speculative page-header search.

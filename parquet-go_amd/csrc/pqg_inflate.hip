@@ -25,6 +25,7 @@
 
 #include "pqg_common.h"
 #include "pqg_device.h"
+#include "pqg_crc.h"
 #include "pqg_hybrid.h"
 
 namespace pqg {
@@ -52,7 +53,6 @@ constexpr int kRingSmall = PQG_INFLATE_RING;  // k_inflate_s: older history is r
 constexpr int kInStage = 1024;    // compressed bytes staged in LDS per refill
 constexpr int kInflateRedo = 0x7ffe;  // k_inflate_s: a page for the 32 KiB-ring pass (not a status)
 constexpr int kFastBits = 9;
-constexpr uint32_t kCrcPoly = 0xedb88320u;  // CRC-32 (IEEE, reflected): gzip trailer
 
 struct Huff {
   uint16_t count[16];    // codes per length
@@ -83,36 +83,7 @@ __device__ __forceinline__ uint32_t dist_base(uint32_t ds, uint32_t ext) {
 }
 __device__ const uint8_t kClOrder[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
 
-// a * b mod P over GF(2), reflected (bit 31 = x^0): zlib's multmodp,
-// branch-free (32 fixed steps: the lanes of a CRC combine hold different a)
-__host__ __device__ constexpr uint32_t multmodp(uint32_t a, uint32_t b) {
-  uint32_t p = 0;
-#pragma unroll 4
-  for (int i = 0; i < 32; i++) {
-    p ^= b & (0u - ((a >> (31 - i)) & 1u));
-    b = (b >> 1) ^ (kCrcPoly & (0u - (b & 1u)));
-  }
-  return p;
-}
-// x^(2^k) mod P, k = 0..31 (zlib's x2n_table; the period is 32)
-struct X2n {
-  uint32_t v[32];
-};
-constexpr X2n make_x2n() {
-  X2n t{};
-  uint32_t p = 1u << 30;  // x^1
-  t.v[0] = p;
-  for (int k = 1; k < 32; k++) t.v[k] = p = multmodp(p, p);
-  return t;
-}
-__device__ const X2n kX2n = make_x2n();
-// x^(8 n) mod P: one multiply per set bit of n (zlib's x2nmodp(n, 3))
-__device__ __forceinline__ uint32_t x8nmodp(uint64_t n) {
-  uint32_t p = 1u << 31;  // x^0
-  for (int k = 3; n; k++, n >>= 1)
-    if (n & 1) p = multmodp(kX2n.v[k & 31], p);
-  return p;
-}
+// (CRC-32 arithmetic: multmodp, x8nmodp, kCrcPoly in pqg_crc.h, shared with k_page_crc)
 
 }  // namespace
 

@@ -18,6 +18,7 @@
 
 #include "../../include/pqgpu.h"
 #include "pqg_common.h"
+#include "pqg_crc.h"
 #include "pqg_lz4.h"
 #include "pqg_zstd.h"
 
@@ -46,6 +47,12 @@ __global__ void k_page_chain(JobDev* jobs, PageDev* pages, const Cand* cands, co
 __global__ void k_scan_pages(JobDev* jobs, PageDev* pages, int n_jobs, int prewalk, int stride);
 __global__ void k_page_list(JobDev* jobs, PageDev* pages, int n_jobs, int* list, int list_cap, int* total,
                             int* queues);
+__global__ void k_crc_plan(const JobDev* jobs, const PageDev* pages, const int* list, const int* total, int n_recs,
+                           crc::Rec* recs, crc::TileRec* tiles, int tile_cap, int* tile_ctr);
+__global__ void k_page_crc(const crc::Rec* recs, const crc::TileRec* tiles, const int* tile_ctr, int tile_cap, int* queue,
+                           uint32_t* raws);
+__global__ void k_crc_fin(PageDev* pages, const int* list, const int* total, int n_recs, crc::Rec* recs,
+                          const uint32_t* raws);
 __global__ void k_snappy(JobDev* jobs, PageDev* pages, const int* list, const int* total, int* queue,
                          uint8_t* scratch);
 __global__ void k_inflate(JobDev* jobs, PageDev* pages, const int* list, const int* total, int* queue,
@@ -92,6 +99,7 @@ __global__ void k_dict_plan(JobDev* jobs, PageDev* pages, const PartRec* parts, 
 __global__ void k_dict4(PageDev* pages, const int* total, int* queue, const VRec* recs, int big);
 __global__ void k_dict4_big(PageDev* pages, const int* total, int* queue, const VRec* recs);
 constexpr int kBigDictThreads = 512;
+constexpr int kCrcThreads = 256;  // k_page_crc: kCrcWaves waves share the tables (pqg_crc.hip)
 __global__ void k_finalize(JobDev* jobs, int n_jobs, const PageDev* pages);
 __global__ void k_str_dict(JobDev* jobs, PageDev* pages, int64_t* doffs_arena);
 __global__ void k_str_count(JobDev* jobs, PageDev* pages, PartRec* parts, const int* total, int* queue,
@@ -217,6 +225,16 @@ struct pqg_ctx {
   bool lz4_batch = PQG_LZ4_BATCH;  // LZ4_RAW pages by k_lz4_batch (step B), not k_lz4 (step A); PQG_LZ4_BATCH=0/1 in the
                                    // environment overrides the build's choice for a context (tests, tools/lz4_probe.py)
   DevBuf zstd_ws;         // k_zstd: a literal workspace (zstd::kWsBytes) per wave of its grid
+  // K1c page checksums (pqg_crc.hip); nothing of it is planned or launched while verify_crc is off
+  bool verify_crc = false;  // pqg_set_verify_crc; PQG_VERIFY_CRC=0/1 in the environment sets a context's initial value
+  bool crc_ran = false;     // the last decode ran with verification on (pqg_get_page_crcs)
+  bool crc_timed = false;   // ... and recorded ev_crc
+  int crc_per_cu = 8;       // resident k_page_crc workgroups per CU (LDS-bound: its tables), from the occupancy query
+  DevBuf crc_recs, crc_tiles, crc_raws;  // crc::Rec per page-table entry, crc::TileRec / raw register per tile
+  int64_t crc_tile_cap = 0;
+  int64_t crc_cap_limit = 0;  // PQG_CRC_TILE_CAP (tests): at most this many tile records per region, so that pages find no room
+  DevBuf crc_one;           // pqg_crc32: its record, tile table, registers, counter and queue
+  hipEvent_t ev_crc[2];
   DevBuf jobs, pages, list, counters, def_arena, rep_arena, value_arena, scratch;
   DevBuf tile_job;  // K1: tile -> job
   DevBuf tile_count, tile_okc, tile_off, tile_okoff, cand_pos, cands, succ, idx2slot, ok2slot, order;  // K1
@@ -284,6 +302,7 @@ const char* pqg_status_string(int s) {
     case PQG_ERR_GZIP: return "gzip: invalid data";
     case PQG_ERR_ZSTD: return "zstd: invalid frame / block / checksum";
     case PQG_ERR_LZ4: return "lz4: invalid block";
+    case PQG_ERR_CRC: return "page checksum mismatch";
     case PQG_ERR_CAPACITY: return "capacity";
     case PQG_ERR_INVALID_ARG: return "invalid argument";
     case PQG_ERR_HIP: return "HIP runtime error";
@@ -308,6 +327,9 @@ int pqg_ctx_create(int device, pqg_ctx** out) {
   }
   for (auto& e : c->ev) hipEventCreate(&e);
   for (auto& e : c->ev_k8) hipEventCreate(&e);
+  for (auto& e : c->ev_crc) hipEventCreate(&e);
+  if (const char* e = getenv("PQG_VERIFY_CRC")) c->verify_crc = atoi(e) != 0;
+  if (const char* e = getenv("PQG_CRC_TILE_CAP")) c->crc_cap_limit = atoi(e) > 0 ? atoi(e) : 0;
   if (const char* e = getenv("PQG_DICT4")) c->dict4 = atoi(e) != 0;
   if (const char* e = getenv("PQG_DICT_BIG")) c->dict_big = atoi(e) != 0;
   if (const char* e = getenv("PQG_STRIDE")) c->stride = atoi(e) != 0;
@@ -343,6 +365,10 @@ int pqg_ctx_create(int device, pqg_ctx** out) {
           &occ, c->lz4_batch ? reinterpret_cast<const void*>(&k_lz4_batch) : reinterpret_cast<const void*>(&k_lz4), 64, 0) == hipSuccess &&
       occ > 0)
     c->lz4_per_cu = occ;
+  occ = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void*>(&k_page_crc), kCrcThreads, 0) ==
+          hipSuccess && occ > 0)
+    c->crc_per_cu = occ;
   // counters: ctr[0..1023] + the kQShards-sharded work queues and the per-stage flags
   if (c->counters.grow(sizeof(int) * (size_t)(1024 + kQueueSlots * kQueueInts))) {
     pqg_ctx_destroy(c);
@@ -358,12 +384,14 @@ void pqg_ctx_destroy(pqg_ctx* c) {
   hipStreamSynchronize(c->stream);
   for (auto& e : c->ev) hipEventDestroy(e);
   for (auto& e : c->ev_k8) hipEventDestroy(e);
+  for (auto& e : c->ev_crc) hipEventDestroy(e);
   for (DevBuf* b : {&c->jobs, &c->pages, &c->list, &c->counters, &c->def_arena, &c->rep_arena, &c->value_arena,
                     &c->scratch, &c->streams, &c->runs, &c->blks, &c->cand_list, &c->vlists, &c->tile_count, &c->tile_okc, &c->tile_off, &c->tile_okoff, &c->cand_pos, &c->cands, &c->succ, &c->idx2slot,
                     &c->ok2slot, &c->order, &c->asm_seg, &c->offs_arena, &c->doffs_arena, &c->page_stage,
                     &c->blk_src, &c->blk_dst, &c->blk_meta, &c->tile_job, &c->sn_subs, &c->sn_segpage, &c->sn_F,
                     &c->blk_subs, &c->blk_segpage, &c->blk_F, &c->vrecs, &c->parts, &c->lev_long, &c->lev_pieces,
-                    &c->walk_long, &c->nn_sums, &c->nn_jobs, &c->zstd_ws})
+                    &c->walk_long, &c->nn_sums, &c->nn_jobs, &c->zstd_ws, &c->crc_recs, &c->crc_tiles, &c->crc_raws,
+                    &c->crc_one})
     b->release();
   if (c->h_jobs) hipHostFree(c->h_jobs);
   hipStreamDestroy(c->stream);
@@ -530,6 +558,18 @@ static int plan_batch(pqg_ctx* c) {
       c->offs_arena.grow(sizeof(int64_t) * (size_t)offs_total + 64) ||
       c->doffs_arena.grow(sizeof(int64_t) * (size_t)doffs_total + 64))
     return PQG_ERR_HIP;
+  if (c->verify_crc) {
+    // pages do not overlap: a page of s bytes has at most s / kTile + 2 tiles (a table too small for
+    // a chunk whose pages do overlap is no error: k_crc_fin reads what did not fit itself)
+    int64_t ct = 2 * page_total + 64;
+    for (int i = 0; i < n; i++) ct += std::max<int64_t>(0, c->cur[(size_t)i].data_len) / crc::kTile;
+    c->crc_tile_cap = std::min<int64_t>(ct, INT32_MAX / kQShards);
+    if (c->crc_cap_limit > 0) c->crc_tile_cap = std::min(c->crc_tile_cap, c->crc_cap_limit);
+    if (c->crc_recs.grow(sizeof(crc::Rec) * (size_t)std::max<int64_t>(page_total, 1)) ||
+        c->crc_tiles.grow(sizeof(crc::TileRec) * kQShards * (size_t)c->crc_tile_cap) ||  // a region per counter shard
+        c->crc_raws.grow(sizeof(uint32_t) * kQShards * (size_t)c->crc_tile_cap))
+      return PQG_ERR_HIP;
+  }
   c->total_tiles = tile_total;
   int64_t max_tiles = 0, max_pages = 0;
   for (int i = 0; i < n; i++) {
@@ -624,6 +664,25 @@ static int launch_pipeline(pqg_ctx* c) {
   hipLaunchKernelGGL(k_page_list, page_grid, dim3(1024), 0, s, jobs, pages, n, list,
                      (int)std::min<int64_t>(c->list_cap, INT32_MAX), ctr, ctr + 8);
   if (c->timed) hipEventRecord(c->ev[2], s);
+  c->crc_ran = c->verify_crc;
+  c->crc_timed = c->verify_crc && c->timed;
+  if (c->verify_crc) {
+    // K1c (pqg_crc.hip), before any decompressor: a page that fails gets read_status = kCRC here, and
+    // they, the level stage and the values stages skip pages whose read phase failed; k_finalize
+    // then ranks it among the read-phase errors.  Part of the decompression stage's time (ev[2] .. ev[3]).
+    crc::Rec* recs = (crc::Rec*)c->crc_recs.p;
+    crc::TileRec* ctiles = (crc::TileRec*)c->crc_tiles.p;
+    uint32_t* raws = (uint32_t*)c->crc_raws.p;
+    int* tile_ctr = Q(kQueueCrc) + kCrcTileCtr;
+    const unsigned page_waves = (unsigned)std::max<int64_t>(1, std::min<int64_t>(c->list_cap, (int64_t)c->num_cus * 16));
+    if (c->timed) hipEventRecord(c->ev_crc[0], s);
+    hipLaunchKernelGGL(k_crc_plan, dim3(page_waves), dim3(64), 0, s, jobs, pages, list, ctr, 0, recs, ctiles,
+                       (int)c->crc_tile_cap, tile_ctr);
+    hipLaunchKernelGGL(k_page_crc, dim3(qgrid((int64_t)c->num_cus * c->crc_per_cu)), dim3(kCrcThreads), 0, s, recs, ctiles, tile_ctr,
+                       (int)c->crc_tile_cap, Q(kQueueCrc), raws);
+    hipLaunchKernelGGL(k_crc_fin, dim3(page_waves), dim3(64), 0, s, pages, list, ctr, 0, recs, raws);
+    if (c->timed) hipEventRecord(c->ev_crc[1], s);
+  }
   bool any_snappy = false, any_gzip = false, any_zstd = false, any_lz4 = false;
   for (int i = 0; i < n; i++) {
     any_snappy |= c->cur[(size_t)i].col.codec == PQG_CODEC_SNAPPY;
@@ -1342,6 +1401,86 @@ int pqg_debug_job(pqg_ctx* c, int job, int64_t* out, int cap) {
 int pqg_set_timing(pqg_ctx* c, int on) {
   if (!c) return PQG_ERR_INVALID_ARG;
   c->timed = on != 0;
+  return PQG_OK;
+}
+
+int pqg_set_verify_crc(pqg_ctx* c, int on) {
+  if (!c) return PQG_ERR_INVALID_ARG;
+  c->verify_crc = on != 0;
+  return PQG_OK;
+}
+
+int pqg_last_crc_ms(pqg_ctx* c, float* ms) {
+  if (!c || !ms) return PQG_ERR_INVALID_ARG;
+  *ms = 0.f;
+  if (c->crc_timed && hipEventElapsedTime(ms, c->ev_crc[0], c->ev_crc[1]) != hipSuccess) *ms = 0.f;
+  return PQG_OK;
+}
+
+int pqg_get_page_crcs(pqg_ctx* c, int job, pqg_page_crc* out, int cap) {
+  if (!c || job < 0 || job >= c->n_jobs || (!out && cap > 0)) return PQG_ERR_INVALID_ARG;
+  hipSetDevice(c->device);
+  const JobDev& d = c->h_jobs[job];
+  int np = std::min<int>(d.n_out_pages, d.page_cap);  // the pages pqg_get_pages reports
+  if (d.status == PQG_ERR_CAPACITY) np = 0;
+  np = std::min(np, std::max(cap, 0));
+  std::vector<crc::Rec> tmp((size_t)std::max(np, 0));
+  if (np > 0 && c->crc_ran) {
+    if (hipMemcpyAsync(tmp.data(), (crc::Rec*)c->crc_recs.p + d.page_base, sizeof(crc::Rec) * (size_t)np,
+                       hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess)
+      return PQG_ERR_HIP;
+  }
+  for (int i = 0; i < np; i++) {
+    pqg_page_crc& o = out[i];
+    memset(&o, 0, sizeof(o));
+    o.state = PQG_CRC_NOT_CHECKED;
+    if (!c->crc_ran) continue;
+    const crc::Rec& r = tmp[(size_t)i];
+    if (r.state == crc::kNoField || r.state == crc::kVerified || r.state == crc::kMismatch) {
+      o.state = r.state;
+      o.stored = r.stored;
+      o.computed = r.computed;
+    }
+  }
+  return np;
+}
+
+int pqg_crc32(pqg_ctx* c, const uint8_t* dev, int64_t n, uint32_t* out) {
+  if (!c || !out || n < 0 || (!dev && n > 0)) return PQG_ERR_INVALID_ARG;
+  *out = 0;
+  if (n == 0) return PQG_OK;
+  hipSetDevice(c->device);
+  const int64_t nt = crc::num_tiles((uintptr_t)dev, n);
+  if (nt > INT32_MAX) return PQG_ERR_UNSUPPORTED;
+  // [Rec][counter + queue ints][TileRec nt][raw nt]
+  const size_t o_q = sizeof(crc::Rec), o_t = o_q + sizeof(int) * kQueueInts, o_r = o_t + sizeof(crc::TileRec) * (size_t)nt;
+  if (c->crc_one.grow(o_r + sizeof(uint32_t) * (size_t)nt)) return PQG_ERR_HIP;
+  uint8_t* b = (uint8_t*)c->crc_one.p;
+  crc::Rec* rec = (crc::Rec*)b;
+  int* q = (int*)(b + o_q);
+  crc::TileRec* tiles = (crc::TileRec*)(b + o_t);
+  uint32_t* raws = (uint32_t*)(b + o_r);
+  crc::Rec h;
+  memset(&h, 0, sizeof(h));
+  h.p = dev;
+  h.n = n;
+  h.state = crc::kPending;
+  if (hipMemcpyAsync(rec, &h, sizeof(h), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+      hipMemsetAsync(q, 0, sizeof(int) * kQueueInts, c->stream) != hipSuccess)
+    return PQG_ERR_HIP;
+  const int cap = (int)(c->crc_cap_limit > 0 ? std::min<int64_t>(nt, c->crc_cap_limit) : nt);
+  hipLaunchKernelGGL(k_crc_plan, dim3(1), dim3(64), 0, c->stream, nullptr, nullptr, nullptr, nullptr, 1, rec, tiles,
+                     cap, q + kCrcTileCtr);
+  hipLaunchKernelGGL(k_page_crc, dim3(qgrid(std::min<int64_t>((nt + 3) / 4, (int64_t)c->num_cus * c->crc_per_cu))), dim3(kCrcThreads), 0,
+                     c->stream, rec, tiles, q + kCrcTileCtr, cap, q, raws);
+  hipLaunchKernelGGL(k_crc_fin, dim3(1), dim3(64), 0, c->stream, nullptr, nullptr, nullptr, 1, rec, raws);
+  if (hipGetLastError() != hipSuccess) return PQG_ERR_HIP;
+  if (hipMemcpyAsync(&h, rec, sizeof(h), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+      hipStreamSynchronize(c->stream) != hipSuccess)
+    return PQG_ERR_HIP;
+  if (h.state != crc::kVerified && h.state != crc::kMismatch) return PQG_ERR_HIP;
+  *out = h.computed;
   return PQG_OK;
 }
 

@@ -36,6 +36,10 @@ def lib():
         "pqg_get_pages": ([P, I, C.POINTER(abi.PageInfo), I], I),
         "pqg_last_timings": ([P, C.POINTER(C.c_float), I], I),
         "pqg_set_timing": ([P, I], I),
+        "pqg_set_verify_crc": ([P, I], I),
+        "pqg_get_page_crcs": ([P, I, C.POINTER(abi.PageCrc), I], I),
+        "pqg_crc32": ([P, P, I64, C.POINTER(C.c_uint32)], I),
+        "pqg_last_crc_ms": ([P, C.POINTER(C.c_float)], I),
         "pqg_debug_job": ([P, I, C.POINTER(I64), I], I),
         "pqg_debug_counters": ([P, C.POINTER(C.c_uint64), I], I),
         "pqg_bench_decode": ([P, C.POINTER(abi.ChunkJob), I, I, C.POINTER(C.c_float), C.POINTER(C.c_float), I], I),
@@ -59,7 +63,11 @@ def lib():
         "pqg_file_schema_node": ([P, I, C.POINTER(abi.SchemaNode)], I),
     }
     for name, (args, res) in sig.items():
-        fn = getattr(L, name)
+        # a library named by PQG_LIB may be an older build (A/B runs against a parent's library):
+        # what it lacks fails at the call; the tree's own library must have every symbol
+        fn = getattr(L, name, None) if os.environ.get("PQG_LIB") else getattr(L, name)
+        if fn is None:
+            continue
         fn.argtypes = args
         fn.restype = res
     _lib = L
@@ -71,7 +79,7 @@ EXPORTED = [
     "pqg_memcpy_h2d", "pqg_memcpy_d2h", "pqg_decode_chunks_async", "pqg_sync", "pqg_decode_chunks",
     "pqg_get_pages", "pqg_last_timings", "pqg_set_timing", "pqg_debug_job", "pqg_debug_counters", "pqg_bench_decode", "pqg_assemble",
     "pqg_assemble_list", "pqg_assemble_nested", "pqg_last_assemble_ms", "pqg_decode_page", "pqg_block_decompress", "pqg_pack_levels", "pqg_file_open", "pqg_file_open_tail",
-    "pqg_file_close",
+    "pqg_file_close", "pqg_set_verify_crc", "pqg_get_page_crcs", "pqg_crc32", "pqg_last_crc_ms",
     "pqg_file_num_columns", "pqg_file_num_row_groups", "pqg_file_num_rows", "pqg_file_row_group_rows",
     "pqg_file_column", "pqg_file_chunk", "pqg_file_num_schema_nodes", "pqg_file_schema_node",
 ]

@@ -39,6 +39,7 @@ STATUS = {
     -15: "GZIP",
     -16: "ZSTD",
     -17: "LZ4",
+    -18: "CRC",
     -20: "CAPACITY",
     -21: "INVALID_ARG",
     -22: "HIP",
@@ -123,6 +124,14 @@ class PageInfo(C.Structure):
         ("status", C.c_int32),
         ("flags", C.c_int32),
     ]
+
+
+CRC_NONE, CRC_VERIFIED, CRC_MISMATCH, CRC_NOT_CHECKED = 0, 1, 2, 3
+
+
+class PageCrc(C.Structure):
+    """pqg_page_crc (include/pqgpu.h): PageHeader.crc of one page and what the GPU computed."""
+    _fields_ = [("stored", C.c_uint32), ("computed", C.c_uint32), ("state", C.c_int32), ("reserved", C.c_int32)]
 
 
 class ColumnInfo(C.Structure):

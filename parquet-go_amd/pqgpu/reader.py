@@ -234,6 +234,31 @@ class GpuDecoder:
             raise PqgError(k, "pqg_get_pages")
         return [buf[i] for i in range(k)]
 
+    # ---- page checksums (PageHeader.crc)
+    def set_verify_crc(self, on):
+        """Verify PageHeader.crc of every page that carries one, in later decodes on this context
+        (off by default; a mismatch is the page's read-phase error PQG_ERR_CRC, -18)."""
+        _check(self.L.pqg_set_verify_crc(self.ctx, 1 if on else 0), "pqg_set_verify_crc")
+
+    def page_crcs(self, job_index, cap=1 << 20):
+        """[abi.PageCrc] of the pages `pages(job_index)` reports, in the same order."""
+        buf = (abi.PageCrc * cap)()
+        k = self.L.pqg_get_page_crcs(self.ctx, job_index, buf, cap)
+        if k < 0:
+            raise PqgError(k, "pqg_get_page_crcs")
+        return [buf[i] for i in range(k)]
+
+    def crc32(self, ptr, n):
+        """zlib.crc32 of the device bytes [ptr, ptr + n), computed by the page-checksum kernel."""
+        out = C.c_uint32()
+        _check(self.L.pqg_crc32(self.ctx, C.c_void_p(ptr), n, C.byref(out)), "pqg_crc32")
+        return out.value
+
+    def last_crc_ms(self):
+        ms = C.c_float()
+        _check(self.L.pqg_last_crc_ms(self.ctx, C.byref(ms)), "pqg_last_crc_ms")
+        return ms.value
+
     def debug_job(self, job_index):
         """(serial_walk, candidates, pages, scratch_bytes, pipeline_launches) of the last decode."""
         out = (C.c_int64 * 5)()
@@ -479,11 +504,15 @@ class FileReader:
     columns of a file (dotted paths, schema.isSelected schema.go:296-312; none =
     all), decoded one row group at a time on the GPU.  `source` is the file's
     bytes or a path (then only the footer and the selected chunks are read);
-    each row group uploads only its selected chunks' bytes (span_jobs)."""
+    each row group uploads only its selected chunks' bytes (span_jobs).
+    `verify_crc`: check PageHeader.crc of the pages that carry one (GpuDecoder.set_verify_crc);
+    a page that fails makes the readers that raise PqgError raise it with code -18 (CRC)."""
 
-    def __init__(self, source, *columns, device=0, decoder=None):
+    def __init__(self, source, *columns, device=0, decoder=None, verify_crc=False):
         self.file = ParquetFile.open(source) if isinstance(source, (str, os.PathLike)) else ParquetFile(source)
         self.dec = decoder or GpuDecoder(device)
+        if verify_crc:
+            self.dec.set_verify_crc(True)
         self.selected = self._select(columns)
         self.row_group_position = 0
         self.uploaded_bytes = 0   # H2D bytes so far (projection pushdown check)
