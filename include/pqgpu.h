@@ -108,6 +108,8 @@ enum {
   PQG_ERR_FIXED_LEN = -14,    /* DELTA_BYTE_ARRAY on FIXED_LEN_BYTE_ARRAY: a value  */
                               /* whose length is not type_length (the reference     */
                               /* returns it; the fixed-width output cannot hold it) */
+  PQG_ERR_NOT_DICT = -19,     /* PQG_COL_KEEP_DICT: a data page that is not dictionary */
+                              /* encoded (a read-phase error of that page)            */
   PQG_ERR_CAPACITY = -20,     /* internal: arena too small; host grows and retries  */
   PQG_ERR_INVALID_ARG = -21,
   PQG_ERR_HIP = -22,
@@ -140,7 +142,24 @@ typedef struct pqg_column_desc {
   int32_t max_rep;       /* Column.MaxRepetitionLevel()  (0..255)                */
   int32_t codec;         /* ColumnMetaData.codec                                 */
   int32_t flags;         /* bit0: unsigned (uint32/uint64 Go type; bits identical) */
+                         /* bit1: PQG_COL_KEEP_DICT                               */
 } pqg_column_desc;
+
+/* pqg_column_desc.flags.  PQG_COL_KEEP_DICT (pqg_decode_chunks[_async] / pqg_sync only):
+ * the chunk is not materialised.  Its result holds the dictionary keys the file stores:
+ * value_width = 4, `values` = num_values little-endian int32 keys, dense, in page order,
+ * offsets = NULL, values_bytes = 4 * num_values; levels, num_slots, num_values, num_pages
+ * and the page table are those of the decode without the flag.  The dictionary itself
+ * comes from pqg_get_dictionary.  A data page of such a job whose encoding is not
+ * RLE_DICTIONARY / PLAIN_DICTIONARY (the PLAIN pages after a writer's dictionary overflow,
+ * DELTA_*, BYTE_STREAM_SPLIT) fails its read phase with PQG_ERR_NOT_DICT; every other
+ * error is the one the decode without the flag reports, on the same page.  BOOLEAN
+ * columns have no dictionary encoding: the flag on one is PQG_ERR_INVALID_ARG at submit,
+ * and so is the flag in pqg_decode_page. */
+enum {
+  PQG_COL_UNSIGNED = 1,
+  PQG_COL_KEEP_DICT = 2
+};
 
 /* One column chunk to decode.  `data` points at the chunk's first page
  * (DictionaryPageOffset when set, else DataPageOffset — chunk_reader.go:332-340).
@@ -185,7 +204,8 @@ typedef struct pqg_chunk_result {
   int32_t error_page;  /* index into the page list of the failing page, -1 if none */
   int32_t num_pages;   /* pages seen (dictionary page included)                    */
   int32_t value_width; /* bytes per value; 0 = variable length (offsets)           */
-  int32_t col_flags;   /* the job's pqg_column_desc.flags, echoed: bit0 unsigned   */
+  int32_t col_flags;   /* the job's pqg_column_desc.flags, echoed: bit0 unsigned,  */
+                       /* bit1 PQG_COL_KEEP_DICT (values are int32 keys)           */
                        /* (the Go adapter boxes uint32/uint64 from it, as          */
                        /* int32PlainDecoder.unSigned does, type_int32.go:29-33)    */
   int32_t reserved;
@@ -291,6 +311,28 @@ int pqg_pack_levels(pqg_ctx* ctx, const uint8_t* levels, int64_t n, int max_leve
 /* After pqg_sync: page table of job `job` (host copy).  Returns pages written
  * or a negative status. */
 int pqg_get_pages(pqg_ctx* ctx, int job, pqg_page_info* out, int cap);
+
+/* The dictionary of a PQG_COL_KEEP_DICT job, after the batch's pqg_sync and until the
+ * next decode on the ctx (PQG_ERR_INVALID_ARG for a job without the flag).  Pointers are
+ * DEVICE pointers.  Fixed-width columns: `values` are the count entries of value_width
+ * bytes, read in place as the decoder reads them (the chunk's own bytes, or the ctx
+ * scratch for a compressed dictionary page; the former are the caller's buffer, which must
+ * stay allocated while the dictionary is used), values_bytes = count * value_width -- less
+ * for a truncated INT96 page, whose entry nil_entry has fewer than 12 bytes there and
+ * reads as zero bytes (Q8).  Byte arrays: `values` are the entries' chars back to back
+ * and `offsets` count + 1 int64 (entry i = chars [offsets[i], offsets[i+1])).  A chunk
+ * without a (valid) dictionary page reports count 0, page -1 and NULL pointers. */
+typedef struct pqg_dictionary {
+  const uint8_t* values;   /* DEVICE                                              */
+  const int64_t* offsets;  /* DEVICE, count + 1 entries; NULL for fixed width     */
+  int64_t count;
+  int64_t values_bytes;
+  int32_t value_width;     /* bytes per entry; 0 = byte arrays                    */
+  int32_t nil_entry;       /* the INT96 entry that reads as zero bytes, -1: none  */
+  int32_t page;            /* index of the dictionary page in the page list, -1   */
+  int32_t reserved;
+} pqg_dictionary;
+int pqg_get_dictionary(pqg_ctx* ctx, int job, pqg_dictionary* out);
 
 /* Kernel timing of the last decode (HIP events on the ctx stream), in ms:
  * out[0] = whole pipeline, out[1..] = per stage. Returns the

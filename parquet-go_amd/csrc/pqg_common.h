@@ -40,6 +40,7 @@ enum : int32_t {
   kZSTD = -16,       // zstd: invalid frame, block or checksum
   kLZ4 = -17,        // lz4: a block LZ4_decompress_safe rejects
   kCRC = -18,        // PageHeader.crc does not match the page's bytes (k_crc_fin; only with verification on)
+  kNOT_DICT = -19,   // keep-dictionary job (JobDev.keep_dict): a data page of another encoding than RLE_DICTIONARY
   kCAPACITY = -20,
   kCOMPLEX = -30,   // internal: header needs the serial walk (deep thrift nesting)
 };
@@ -75,7 +76,7 @@ struct PageDev {
   int32_t dict_width;      // RLE_DICTIONARY: index bit width byte
   int32_t hs_rep, hs_def, hs_val;  // hybrid streams of the page (HStream index, -1: none)
   int32_t vmode;           // values stage of the page: 1 4-byte dictionary, 3 DELTA_BINARY_PACKED, 0 other fixed width, 2 variable,
-                           // 5 BYTE_STREAM_SPLIT (kModeBss), -1 none
+                           // 5 BYTE_STREAM_SPLIT (kModeBss), 6 dictionary keys kept as they are (kModeIdx), -1 none
   int64_t run_off, blk_off;  // the page's run-table / block-index region (job-relative, k_page_list)
   // variable-length values (BYTE_ARRAY, FLBA of length 0): chars of the page
   // and their offset in the chunk's chars (exclusive scan over the pages)
@@ -216,6 +217,14 @@ struct JobDev {
   // added theirs.  The block that arrives last finishes the job.  All reset by k_page_list.
   int32_t fin_read, fin_dec, fin_done, nn_done;
   unsigned long long nn_acc, parts_acc;
+  // ---- keep-dictionary jobs (PQG_COL_KEEP_DICT; k_dict_idx, k_dict_export: pqg_dictidx.hip)
+  int32_t keep_dict;       // host: the values are the pages' int32 keys (value_width is 4 then)
+  int32_t entry_width;     // host: bytes per dictionary entry, 0 = variable (value_width of the job without the flag)
+  int64_t dchars_cap, dchars_base;  // byte-array dictionary in Arrow layout: the chars' region of the dictionary-chars arena
+  int64_t need_dchars;              // bytes that region needs (the dictionary page's size)
+  const uint8_t* dict_chars;        // k_dict_export: the chars back to back (null: not exported)
+  const int64_t* dict_aoffs;        // k_dict_export: count + 1 offsets into them
+  int64_t dict_chars_len;           // k_dict_export: bytes of dict_chars (dict_aoffs[count])
 };
 
 // The per-chunk bookkeeping kernels (k_page_chain, k_page_list, k_nn_scan,
@@ -328,6 +337,8 @@ constexpr int kModePresentOff = 1024 + 9 * kQueueInts;
 // BYTE_STREAM_SPLIT pages (k_bss, pqg_bss.hip): their values stage and its flag (4 is the
 // DELTA_*_BYTE_ARRAY flag, 8 kPresentBigDict)
 constexpr int kModeBss = 5;
+// RLE_DICTIONARY pages of keep-dictionary jobs (k_dict_idx, pqg_dictidx.hip): their values stage and its flag
+constexpr int kModeIdx = 6;
 // the serial snappy pass (k_snappy after the split decode) pulls its own queue
 constexpr int kQueueSnapSerial = 10;
 // DELTA_LENGTH_BYTE_ARRAY / DELTA_BYTE_ARRAY lengths (k_str_delta) and values (k_str_dba)
@@ -345,8 +356,9 @@ constexpr int kQueueBss = 20;   // parts of BYTE_STREAM_SPLIT pages (k_bss)
 // the region (between two queue heads, zeroed with them) counts the tile records k_crc_plan reserved
 constexpr int kQueueCrc = 21;
 constexpr int kCrcTileCtr = 1;
-// queue regions zeroed per launch: 0-8, the stage flags (9), 10-21
-constexpr int kQueueSlots = 22;
+constexpr int kQueueDictIdx = 22;  // parts of the pages whose keys are kept (k_dict_idx)
+// queue regions zeroed per launch: 0-8, the stage flags (9), 10-22
+constexpr int kQueueSlots = 23;
 constexpr int kPresentBigDict = 8;  // stage flag (kModePresentOff + 8): a page for k_dict4_big
 
 // Scan tiles of the speculative page-header search.

@@ -750,12 +750,19 @@ __device__ __forceinline__ PageStreams page_setup(const JobDev& job, const PageD
     if (writer) pages[pidx].read_status = r.e;
     return r;
   }
+  // a keep-dictionary job takes RLE_DICTIONARY pages only (the scan maps PLAIN_DICTIONARY to it)
+  if (job.keep_dict && pg.encoding != 8) {
+    r.e = kNOT_DICT;
+    if (writer) pages[pidx].read_status = r.e;
+    return r;
+  }
   const int64_t n = pg.num_values;
   const int64_t vn = blen - vpos;
   gcu8 val = block + vpos;
   r.val = val;
   r.val_n = vn;
-  r.vmode = pg.encoding == 9 && job.value_width > 0                    ? kModeBss
+  r.vmode = job.keep_dict                                              ? kModeIdx
+            : pg.encoding == 9 && job.value_width > 0                  ? kModeBss
             : job.value_width == 0 || (pg.encoding == 7 && job.type == 7) ? 2
             : (pg.encoding == 8 && job.value_width == 4)                ? 1
             : pg.encoding == 5                                          ? 3
@@ -783,7 +790,7 @@ __device__ __forceinline__ PageStreams page_setup(const JobDev& job, const PageD
     // value-stage page lists: 4-byte dictionary pages (the hot path, a kernel
     // of its own), variable-length values (pqg_strings.hip) and everything else
     // (DELTA_BYTE_ARRAY on FLBA: the strings stage, values of type_length bytes);
-    // BYTE_STREAM_SPLIT pages: k_bss
+    // BYTE_STREAM_SPLIT pages: k_bss; the pages of keep-dictionary jobs: k_dict_idx
     const int vm = r.vmode;
     P.vmode = vm;
     int* present = const_cast<int*>(total) + kModePresentOff;

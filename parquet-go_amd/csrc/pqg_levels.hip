@@ -527,7 +527,7 @@ __device__ void resolve_dictionary(JobDev& job, PageDev* pages, uint8_t* scratch
       dp.scratch_offset >= 0 ? scratch + job.scratch_base + dp.scratch_offset : job.data + dp.payload_offset;
   const int64_t blen = dp.usize;
   const int64_t cnt = dp.num_values;
-  const int w = job.value_width;
+  const int w = job.keep_dict ? job.entry_width : job.value_width;
   dp.block = blk;
   dp.block_len = blen;
   int st = kOK;
@@ -546,6 +546,10 @@ __device__ void resolve_dictionary(JobDev& job, PageDev* pages, uint8_t* scratch
     flags = 2;
     job.need_doffs = (cnt < blen / 4 ? cnt : blen / 4) + 2;
     if (job.need_doffs > job.doffs_cap) job.status = kCAPACITY;
+    if (job.keep_dict) {  // the entries' chars, compacted by k_dict_export: fewer than the page's bytes
+      job.need_dchars = blen;
+      if (blen > job.dchars_cap) job.status = kCAPACITY;
+    }
   }
   if (st == kOK) {
     job.flags |= flags;

@@ -93,6 +93,10 @@ __global__ void k_values(JobDev* jobs, PageDev* pages, const PartRec* parts, con
                          uint8_t* value_arena, const HStream* streams, const RunEnt* runs, const BlockDesc* blks);
 __global__ void k_bss(JobDev* jobs, PageDev* pages, const PartRec* parts, const int* total, int* queue,
                       uint8_t* value_arena);
+__global__ void k_dict_idx(JobDev* jobs, PageDev* pages, const PartRec* parts, const int* total, int* queue,
+                           uint8_t* value_arena, const HStream* streams, const RunEnt* runs, const BlockDesc* blks);
+__global__ void k_dict_export(JobDev* jobs, const PageDev* pages, int64_t* aoffs_arena, uint8_t* dchars_arena);
+constexpr int kExportGridY = 16, kExportThreads = 256;  // k_dict_export (pqg_dictidx.hip)
 __global__ void k_dict_plan(JobDev* jobs, PageDev* pages, const PartRec* parts, const int* total,
                             uint8_t* value_arena, const HStream* streams, const RunEnt* runs, const BlockDesc* blks,
                             VRec* recs);
@@ -163,17 +167,23 @@ constexpr int kMaxAttempts = 6;  // decode + up to 5 arena grows in one pqg_sync
 
 // Arena capacities of one chunk job (see plan_batch); 0 = use the planner's estimate.
 struct Caps {
-  int64_t pages = 0, slots = 0, scratch = 0, values = 0, runs = 0, blks = 0, doffs = 0;
+  int64_t pages = 0, slots = 0, scratch = 0, values = 0, runs = 0, blks = 0, doffs = 0, dchars = 0;
 };
 // Capacities learned for a chunk (its bytes, size and value count), kept for
 // later decodes of the same chunk so a grown arena is planned right away.
+// A chunk decoded to keys (PQG_COL_KEEP_DICT) plans other arenas than the same chunk materialised:
+// the two learn apart, so neither decode is planned with the other's sizes.
 struct JobKey {
   uintptr_t data;
   int64_t tcs, hint;
+  int keep;
   bool operator<(const JobKey& o) const {
-    return data != o.data ? data < o.data : tcs != o.tcs ? tcs < o.tcs : hint < o.hint;
+    return data != o.data ? data < o.data : tcs != o.tcs ? tcs < o.tcs : hint != o.hint ? hint < o.hint : keep < o.keep;
   }
 };
+JobKey job_key(const pqg_chunk_job& j) {
+  return JobKey{(uintptr_t)j.data, j.total_compressed_size, j.num_values_hint, (j.col.flags & PQG_COL_KEEP_DICT) ? 1 : 0};
+}
 
 int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
 
@@ -242,6 +252,8 @@ struct pqg_ctx {
   DevBuf cand_list, vlists;
   DevBuf asm_seg;  // K8 per-segment counts + totals
   DevBuf offs_arena, doffs_arena;  // K7: value offsets (int64), dictionary record starts
+  DevBuf aoffs_arena, dchars_arena;  // K4i: byte-array dictionaries in Arrow layout (k_dict_export): offsets (laid out as
+                                     // doffs_arena), chars
   DevBuf page_stage;               // pqg_decode_page: [dictionary page][data page]
   DevBuf blk_src, blk_dst, blk_meta, blk_subs, blk_segpage, blk_F;  // pqg_block_decompress
   DevBuf sn_subs, sn_segpage, sn_F;   // K2 split: sub-block table, segment -> page, segment exits
@@ -269,6 +281,9 @@ struct pqg_ctx {
   bool any_fixed_other = false;         // batch holds fixed-width columns (k_values<0> pages possible)
   bool any_w4 = false;                  // batch holds 4-byte columns (the 4-byte dictionary stage: mode 1 pages)
   bool any_levels = false;              // batch holds columns with levels (long level runs possible)
+  bool any_keep = false;                // batch holds keep-dictionary jobs (PQG_COL_KEEP_DICT: k_dict_idx)
+  bool any_keep_var = false;            // ... of byte arrays (k_str_dict, then k_dict_export)
+  bool any_var_out = false;             // batch holds variable-length columns to materialise (the strings stage past k_str_dict)
   int n_jobs = 0;
   int64_t list_cap = 0;
   hipEvent_t ev[kStages + 1];
@@ -303,6 +318,7 @@ const char* pqg_status_string(int s) {
     case PQG_ERR_ZSTD: return "zstd: invalid frame / block / checksum";
     case PQG_ERR_LZ4: return "lz4: invalid block";
     case PQG_ERR_CRC: return "page checksum mismatch";
+    case PQG_ERR_NOT_DICT: return "keep dictionary: data page is not dictionary encoded";
     case PQG_ERR_CAPACITY: return "capacity";
     case PQG_ERR_INVALID_ARG: return "invalid argument";
     case PQG_ERR_HIP: return "HIP runtime error";
@@ -391,7 +407,7 @@ void pqg_ctx_destroy(pqg_ctx* c) {
                     &c->blk_src, &c->blk_dst, &c->blk_meta, &c->tile_job, &c->sn_subs, &c->sn_segpage, &c->sn_F,
                     &c->blk_subs, &c->blk_segpage, &c->blk_F, &c->vrecs, &c->parts, &c->lev_long, &c->lev_pieces,
                     &c->walk_long, &c->nn_sums, &c->nn_jobs, &c->zstd_ws, &c->crc_recs, &c->crc_tiles, &c->crc_raws,
-                    &c->crc_one})
+                    &c->crc_one, &c->aoffs_arena, &c->dchars_arena})
     b->release();
   if (c->h_jobs) hipHostFree(c->h_jobs);
   hipStreamDestroy(c->stream);
@@ -432,7 +448,7 @@ static int plan_batch(pqg_ctx* c) {
     if (hipHostMalloc((void**)&c->h_jobs, sizeof(JobDev) * (size_t)c->h_jobs_cap) != hipSuccess) return PQG_ERR_HIP;
   }
   int64_t page_total = 0, slot_total = 0, value_total = 0, scratch_total = 0, tile_total = 0, run_total = 0,
-          blk_total = 0, offs_total = 0, doffs_total = 0, seg_total = 0;
+          blk_total = 0, offs_total = 0, doffs_total = 0, seg_total = 0, dchars_total = 0;
   bool any_zstd = false;
   c->plan.resize((size_t)n);
   for (int i = 0; i < n; i++) {
@@ -450,8 +466,11 @@ static int plan_batch(pqg_ctx* c) {
     d.max_rep = in.col.max_rep;
     d.codec = in.col.codec;
     d.has_dict_off = in.has_dict_page_offset;
-    d.value_width = value_width_of(in.col);
-    d.no_prewalk = c->many_pages.count(JobKey{(uintptr_t)in.data, in.total_compressed_size, in.num_values_hint}) ? 1 : 0;
+    // a keep-dictionary job stores int32 keys: a 4-byte value arena, no offsets, no chars
+    d.keep_dict = (in.col.flags & PQG_COL_KEEP_DICT) ? 1 : 0;
+    d.entry_width = value_width_of(in.col);
+    d.value_width = d.keep_dict ? 4 : d.entry_width;
+    d.no_prewalk = c->many_pages.count(job_key(in)) ? 1 : 0;
     int64_t pcap = in.total_compressed_size / 256 + 16;
     if (f.pages > 0) pcap = f.pages;
     pcap = std::min<int64_t>(pcap, (int64_t)1 << 30);
@@ -497,18 +516,25 @@ static int plan_batch(pqg_ctx* c) {
     blk_total += bcap;
     // offsets: variable-length values; FLBA columns too (their DELTA_BYTE_ARRAY
     // pages park prefix / suffix lengths there, k_str_delta)
-    if (d.value_width == 0 || d.type == PQG_FIXED_LEN_BYTE_ARRAY) {
+    if (d.value_width == 0 || (d.type == PQG_FIXED_LEN_BYTE_ARRAY && !d.keep_dict)) {
       d.offs_cap = scap + 1;
       d.offs_base = offs_total;
       offs_total += align_up(scap + 1, 32);
     }
-    if (d.value_width == 0) {
+    if (d.entry_width == 0) {
       // dictionary entries take >= 4 bytes each
       int64_t dcap = std::min<int64_t>(std::max<int64_t>(in.total_uncompressed_size, 0) / 4, 1 << 17) + 64;
       if (f.doffs > 0) dcap = f.doffs;
       d.doffs_cap = dcap;
       d.doffs_base = doffs_total;
       doffs_total += align_up(dcap, 32);
+      if (d.keep_dict) {  // the dictionary's chars (k_dict_export); a larger page: the first decode reports it
+        int64_t ccap = std::min<int64_t>(std::max<int64_t>(in.total_uncompressed_size, 0), 1 << 20) + 64;
+        if (f.dchars > 0) ccap = f.dchars;
+        d.dchars_cap = ccap;
+        d.dchars_base = dchars_total;
+        dchars_total += align_up(ccap, 256);
+      }
     }
     d.tile_base = tile_total;
     d.n_tiles = (int32_t)((lim + kScanTile - 1) / kScanTile);
@@ -557,6 +583,9 @@ static int plan_batch(pqg_ctx* c) {
       c->vrecs.grow(sizeof(VRec) * (size_t)std::max<int64_t>(c->parts_cap, 1)) ||
       c->offs_arena.grow(sizeof(int64_t) * (size_t)offs_total + 64) ||
       c->doffs_arena.grow(sizeof(int64_t) * (size_t)doffs_total + 64))
+    return PQG_ERR_HIP;
+  if (c->any_keep_var &&
+      (c->aoffs_arena.grow(sizeof(int64_t) * (size_t)doffs_total + 64) || c->dchars_arena.grow((size_t)dchars_total + 64)))
     return PQG_ERR_HIP;
   if (c->verify_crc) {
     // pages do not overlap: a page of s bytes has at most s / kTile + 2 tiles (a table too small for
@@ -786,10 +815,24 @@ static int launch_pipeline(pqg_ctx* c) {
     hipLaunchKernelGGL(k_bss, dim3(qgrid(waves)), dim3(64), 0, s, jobs, pages, parts, ctr, Q(kQueueBss),
                        (uint8_t*)c->value_arena.p);
   }
+  // K4i (pqg_dictidx.hip): the pages of keep-dictionary jobs, keys stored as they are.  With a byte-array
+  // job among them the kernel waits for k_str_dict (the entry count of such a dictionary) and counts
+  // in the strings stage's time; no such job in the batch: no launch.
+  auto launch_dict_idx = [&]() {
+    hipLaunchKernelGGL(k_dict_idx, dim3(qgrid(waves)), dim3(64), 0, s, jobs, pages, parts, ctr, Q(kQueueDictIdx),
+                       (uint8_t*)c->value_arena.p, streams, runs, blks);
+  };
+  if (c->any_keep && !c->any_keep_var) launch_dict_idx();
   if (c->timed) hipEventRecord(c->ev[8], s);
-  if (c->any_var) {
-    int64_t* offs = (int64_t*)c->offs_arena.p;
+  if (c->any_var)
     hipLaunchKernelGGL(k_str_dict, dim3(n), dim3(512), 0, s, jobs, pages, (int64_t*)c->doffs_arena.p);
+  if (c->any_keep_var) {
+    launch_dict_idx();
+    hipLaunchKernelGGL(k_dict_export, dim3(n, kExportGridY), dim3(kExportThreads), 0, s, jobs, pages,
+                       (int64_t*)c->aoffs_arena.p, (uint8_t*)c->dchars_arena.p);
+  }
+  if (c->any_var_out) {
+    int64_t* offs = (int64_t*)c->offs_arena.p;
     hipLaunchKernelGGL(k_str_plain, dim3(qgrid(c->num_cus * 4 * 512 / kPwThreads)), dim3(kPwThreads), 0, s, jobs, pages, list, ctr, Q(5), offs);
     hipLaunchKernelGGL(k_str_count, dim3(qgrid(waves)), dim3(64), 0, s, jobs, pages, parts, ctr, Q(4), offs, streams,
                        runs, blks);
@@ -816,6 +859,8 @@ int pqg_decode_chunks_async(pqg_ctx* c, const pqg_chunk_job* jobs, int n_jobs) {
     if (jobs[i].data_len < 0 || jobs[i].total_compressed_size < 0 || (!jobs[i].data && jobs[i].data_len > 0))
       return PQG_ERR_INVALID_ARG;
     if (jobs[i].quirks != 0) return PQG_ERR_INVALID_ARG;  // spec-correct only (quirks: oracle triage mode)
+    // BOOLEAN has no dictionary encoding (chunk_reader.go:143-196): nothing to keep
+    if ((d.flags & PQG_COL_KEEP_DICT) && d.physical_type == PQG_BOOLEAN) return PQG_ERR_INVALID_ARG;
   }
   c->cur.assign(jobs, jobs + n_jobs);
   c->n_jobs = n_jobs;
@@ -825,18 +870,27 @@ int pqg_decode_chunks_async(pqg_ctx* c, const pqg_chunk_job* jobs, int n_jobs) {
   c->any_fixed_other = false;
   c->any_w4 = false;
   c->any_levels = false;
+  c->any_keep = c->any_keep_var = c->any_var_out = false;
   c->prewalk = false;
   for (int i = 0; i < n_jobs; i++) {
-    const JobKey key{(uintptr_t)jobs[i].data, jobs[i].total_compressed_size, jobs[i].num_values_hint};
+    const JobKey key = job_key(jobs[i]);
     auto it = c->learned.find(key);
     if (it != c->learned.end()) c->force[(size_t)i] = it->second;
     c->prewalk |= c->many_pages.find(key) == c->many_pages.end();
+    c->any_levels |= jobs[i].col.max_def > 0 || jobs[i].col.max_rep > 0;
+    if (jobs[i].col.flags & PQG_COL_KEEP_DICT) {
+      // only k_dict_idx takes such a job's pages; a byte-array dictionary still needs k_str_dict
+      c->any_keep = true;
+      c->any_keep_var |= value_width_of(jobs[i].col) == 0;
+      c->any_var |= value_width_of(jobs[i].col) == 0;
+      continue;
+    }
     // the strings stage: variable-length columns, and FLBA (DELTA_BYTE_ARRAY pages)
     c->any_var |= value_width_of(jobs[i].col) == 0 || jobs[i].col.physical_type == PQG_FIXED_LEN_BYTE_ARRAY;
+    c->any_var_out |= value_width_of(jobs[i].col) == 0 || jobs[i].col.physical_type == PQG_FIXED_LEN_BYTE_ARRAY;
     // k_values<0>: every fixed-width column but 4-byte ones with only dictionary pages
     c->any_fixed_other |= value_width_of(jobs[i].col) != 0;
     c->any_w4 |= value_width_of(jobs[i].col) == 4;
-    c->any_levels |= jobs[i].col.max_def > 0 || jobs[i].col.max_rep > 0;
   }
   if (n_jobs == 0) return PQG_OK;
   int e = plan_batch(c);
@@ -876,8 +930,9 @@ int pqg_sync(pqg_ctx* c, pqg_chunk_result* results, int n_jobs) {
       f.runs = std::max<int64_t>(d.run_used + 64, d.run_cap);
       f.blks = std::max<int64_t>(d.blk_used + 64, d.blk_cap);
       f.doffs = std::max<int64_t>(d.need_doffs + 64, d.doffs_cap);
+      f.dchars = std::max<int64_t>(d.need_dchars + 64, d.dchars_cap);
       const pqg_chunk_job& in = c->cur[(size_t)i];
-      c->learned[JobKey{(uintptr_t)in.data, in.total_compressed_size, in.num_values_hint}] = f;
+      c->learned[job_key(in)] = f;
     }
     if (!retry || attempt + 1 >= kMaxAttempts) break;
     int e = plan_batch(c);
@@ -890,7 +945,7 @@ int pqg_sync(pqg_ctx* c, pqg_chunk_result* results, int n_jobs) {
     if (d.status != PQG_ERR_CAPACITY && d.scan_fallback != 2) {  // neither walked nor stride-walked by the prewalk
       if (c->many_pages.size() >= 65536) c->many_pages.clear();  // bounded: a cache, not a record
       const pqg_chunk_job& in = c->cur[(size_t)i];
-      c->many_pages[JobKey{(uintptr_t)in.data, in.total_compressed_size, in.num_values_hint}] = true;
+      c->many_pages[job_key(in)] = true;
     }
     pqg_chunk_result& r = results[i];
     memset(&r, 0, sizeof(r));
@@ -1038,6 +1093,7 @@ int pqg_decode_page(pqg_ctx* c, const pqg_page_job* pj, pqg_chunk_result* result
   if (!c || !pj || !result || !pj->page || pj->page_len <= 0 || pj->dict_page_len < 0 ||
       (pj->dict_page_len > 0 && !pj->dict_page))
     return PQG_ERR_INVALID_ARG;
+  if (pj->col.flags & PQG_COL_KEEP_DICT) return PQG_ERR_INVALID_ARG;  // a chunk-level result (pqg_get_dictionary)
   hipSetDevice(c->device);
   const int64_t dl = pj->dict_page ? pj->dict_page_len : 0, total = dl + pj->page_len;
   // the page (after its dictionary) as a one-page column chunk
@@ -1320,6 +1376,33 @@ int pqg_pack_levels(pqg_ctx* c, const uint8_t* levels, int64_t n, int max_level,
   int e = pqg::pack_levels_launch(c->stream, levels, n, bw, packed);
   if (e) return e;
   return hip_ok(hipStreamSynchronize(c->stream));
+}
+
+int pqg_get_dictionary(pqg_ctx* c, int job, pqg_dictionary* out) {
+  if (!c || !out || job < 0 || job >= c->n_jobs) return PQG_ERR_INVALID_ARG;
+  const JobDev& d = c->h_jobs[job];  // as pqg_sync copied it back
+  if (!d.keep_dict) return PQG_ERR_INVALID_ARG;
+  memset(out, 0, sizeof(*out));
+  out->value_width = d.entry_width;
+  out->nil_entry = -1;
+  out->page = -1;
+  if (d.status == PQG_ERR_CAPACITY || d.dict_page < 0) return PQG_OK;
+  if (d.entry_width == 0) {
+    if (!d.dict_offs || !d.dict_aoffs) return PQG_OK;  // the page's walk failed: no dictionary
+    out->page = d.dict_page;
+    out->count = d.dict_count;
+    out->values = d.dict_chars;
+    out->offsets = d.dict_aoffs;
+    out->values_bytes = d.dict_chars_len;
+    return PQG_OK;
+  }
+  if (!d.dict_data) return PQG_OK;  // the page's read phase failed
+  out->page = d.dict_page;
+  out->count = d.dict_count;
+  out->values = d.dict_data;
+  out->values_bytes = std::min<int64_t>(d.dict_count * d.entry_width, d.dict_len);
+  if (d.flags & 1) out->nil_entry = (int32_t)(d.dict_count - 1);  // INT96, Q8
+  return PQG_OK;
 }
 
 int pqg_get_pages(pqg_ctx* c, int job, pqg_page_info* out, int cap) {

@@ -34,6 +34,7 @@ def lib():
         "pqg_sync": ([P, C.POINTER(abi.ChunkResult), I], I),
         "pqg_decode_chunks": ([P, C.POINTER(abi.ChunkJob), I, C.POINTER(abi.ChunkResult)], I),
         "pqg_get_pages": ([P, I, C.POINTER(abi.PageInfo), I], I),
+        "pqg_get_dictionary": ([P, I, C.POINTER(abi.Dictionary)], I),
         "pqg_last_timings": ([P, C.POINTER(C.c_float), I], I),
         "pqg_set_timing": ([P, I], I),
         "pqg_set_verify_crc": ([P, I], I),
@@ -82,4 +83,5 @@ EXPORTED = [
     "pqg_file_close", "pqg_set_verify_crc", "pqg_get_page_crcs", "pqg_crc32", "pqg_last_crc_ms",
     "pqg_file_num_columns", "pqg_file_num_row_groups", "pqg_file_num_rows", "pqg_file_row_group_rows",
     "pqg_file_column", "pqg_file_chunk", "pqg_file_num_schema_nodes", "pqg_file_schema_node",
+    "pqg_get_dictionary",
 ]

@@ -40,6 +40,7 @@ STATUS = {
     -16: "ZSTD",
     -17: "LZ4",
     -18: "CRC",
+    -19: "NOT_DICT",
     -20: "CAPACITY",
     -21: "INVALID_ARG",
     -22: "HIP",
@@ -51,6 +52,9 @@ ERR_CAPACITY = -20
 STATUS_CODES = {v: k for k, v in STATUS.items()}
 
 FIXED_WIDTH = {BOOLEAN: 1, INT32: 4, INT64: 8, INT96: 12, FLOAT: 4, DOUBLE: 8}
+
+# pqg_column_desc.flags
+COL_UNSIGNED, COL_KEEP_DICT = 1, 2
 
 
 class ColumnDesc(C.Structure):
@@ -102,6 +106,20 @@ class ChunkResult(C.Structure):
         ("rep_levels", C.c_void_p),
         ("values", C.c_void_p),
         ("offsets", C.c_void_p),
+    ]
+
+
+class Dictionary(C.Structure):
+    """pqg_dictionary (include/pqgpu.h): the dictionary of a COL_KEEP_DICT job, device pointers."""
+    _fields_ = [
+        ("values", C.c_void_p),
+        ("offsets", C.c_void_p),
+        ("count", C.c_int64),
+        ("values_bytes", C.c_int64),
+        ("value_width", C.c_int32),
+        ("nil_entry", C.c_int32),
+        ("page", C.c_int32),
+        ("reserved", C.c_int32),
     ]
 
 

@@ -75,6 +75,20 @@ def _bits(bitmap, n):
 _FIXED_DTYPE = {abi.INT32: np.int32, abi.INT64: np.int64, abi.FLOAT: np.float32, abi.DOUBLE: np.float64}
 
 
+def fixed_pylist(raw, physical_type, width, flags, n):
+    """n fixed-width values of `width` bytes in `raw` as Python values."""
+    raw = np.asarray(raw, dtype=np.uint8)
+    if physical_type == abi.BOOLEAN:
+        return [bool(x) for x in raw]
+    if physical_type in _FIXED_DTYPE:
+        dt = _FIXED_DTYPE[physical_type]
+        if flags & 1:
+            dt = {np.int32: np.uint32, np.int64: np.uint64}.get(dt, dt)
+        return raw.view(dt).tolist()
+    b = raw.tobytes()
+    return [b[i * width:(i + 1) * width] for i in range(n)]
+
+
 class NestedColumn:
     """One leaf column in Arrow layout.
 
@@ -84,10 +98,14 @@ class NestedColumn:
     leaf_validity  validity bits of the leaf slots (uint32 words)
     values         fixed-width leaf: num_leaf x value_width bytes, nulls zeroed
     chars, leaf_offsets   byte-array leaf: int64[num_leaf + 1] into chars
+    dictionary     a leaf that kept its dictionary (FileReader's read_dictionary): the
+                   pqgpu.reader.Dictionary; values are then int32 keys (value_width 4, a null
+                   slot's key is 0 and means nothing), else None
     """
 
     def __init__(self, levels, leaf_validity, num_leaf, values=None, value_width=0, chars=None, leaf_offsets=None,
-                 physical_type=None, flags=0, num_rows=None):
+                 physical_type=None, flags=0, num_rows=None, dictionary=None):
+        self.dictionary = dictionary
         self.levels = levels
         self.leaf_validity = leaf_validity
         self.num_leaf = num_leaf
@@ -102,22 +120,15 @@ class NestedColumn:
     def leaf_pylist(self):
         """The leaf slots as Python values, None for a null."""
         valid = _bits(self.leaf_validity, self.num_leaf)
+        if self.dictionary is not None:  # keys: looked up, so the result is the materialised leaf's
+            entries = self.dictionary.pylist(self.physical_type, self.flags)
+            keys = np.asarray(self.values, dtype=np.uint8).view("<i4")[:self.num_leaf].tolist()
+            return [entries[k] if ok else None for k, ok in zip(keys, valid)]
         if self.leaf_offsets is not None:
             b = np.asarray(self.chars, dtype=np.uint8).tobytes()
             o = np.asarray(self.leaf_offsets)
             return [b[o[i]:o[i + 1]] if valid[i] else None for i in range(self.num_leaf)]
-        raw = np.asarray(self.values, dtype=np.uint8)
-        t, w = self.physical_type, self.value_width
-        if t == abi.BOOLEAN:
-            vals = [bool(x) for x in raw]
-        elif t in _FIXED_DTYPE:
-            dt = _FIXED_DTYPE[t]
-            if self.flags & 1:
-                dt = {np.int32: np.uint32, np.int64: np.uint64}.get(dt, dt)
-            vals = raw.view(dt).tolist()
-        else:
-            b = raw.tobytes()
-            vals = [b[i * w:(i + 1) * w] for i in range(self.num_leaf)]
+        vals = fixed_pylist(self.values, self.physical_type, self.value_width, self.flags, self.num_leaf)
         return [v if ok else None for v, ok in zip(vals, valid)]
 
     def to_pylist(self):

@@ -139,11 +139,70 @@ class ParquetFile:
         return job, m
 
 
+class Dictionary:
+    """The dictionary of a column chunk decoded with abi.COL_KEEP_DICT, on the host.
+
+    values       fixed width: count x value_width entry bytes as the page stores them (fewer for a
+                 truncated INT96 page, see nil_entry); byte arrays: the entries' chars back to back
+    offsets      byte arrays: int64[count + 1] into values; else None
+    value_width  bytes per entry, 0 for byte arrays
+    nil_entry    the INT96 entry whose value reads as zero bytes (Q8), -1 if none
+    page         index of the dictionary page in the chunk's page list, -1 if the chunk has none"""
+
+    def __init__(self, values, offsets, count, value_width, nil_entry=-1, page=-1):
+        self.values = values
+        self.offsets = offsets
+        self.count = int(count)
+        self.value_width = int(value_width)
+        self.nil_entry = int(nil_entry)
+        self.page = int(page)
+
+    def table(self):
+        """Fixed width: the entries as a (count, value_width) uint8 array, nil_entry as zeros."""
+        w, n = self.value_width, self.count
+        t = np.zeros(n * w, np.uint8)
+        raw = np.asarray(self.values, dtype=np.uint8).reshape(-1)[:n * w]
+        t[:len(raw)] = raw
+        t = t.reshape(n, w)
+        if 0 <= self.nil_entry < n:
+            t[self.nil_entry] = 0
+        return t
+
+    def pylist(self, physical_type, flags=0):
+        """The entries as Python values (bytes for byte arrays, FLBA and INT96)."""
+        if self.value_width == 0:
+            b = np.asarray(self.values, dtype=np.uint8).tobytes()
+            o = np.asarray(self.offsets, dtype=np.int64).tolist()
+            return [b[o[i]:o[i + 1]] for i in range(self.count)]
+        from .nested import fixed_pylist
+        return fixed_pylist(self.table().reshape(-1), physical_type, self.value_width, flags, self.count)
+
+    def lookup(self, keys):
+        """dictionary[keys] in the layout of a materialised decode: (dense bytes, None) for fixed
+        width, (chars, int64 offsets[len(keys) + 1]) for byte arrays."""
+        keys = np.asarray(keys).astype(np.int64, copy=False)
+        if len(keys) and (keys.min() < 0 or keys.max() >= self.count):
+            raise IndexError("dictionary key out of range")
+        if self.value_width > 0:
+            return np.ascontiguousarray(self.table()[keys]).reshape(-1), None
+        o = np.asarray(self.offsets, dtype=np.int64)
+        lens = (o[1:] - o[:-1])[keys]
+        out = np.zeros(len(keys) + 1, np.int64)
+        np.cumsum(lens, out=out[1:])
+        src = np.repeat(o[:-1][keys] - out[:-1], lens) + np.arange(out[-1], dtype=np.int64)
+        return np.asarray(self.values, dtype=np.uint8)[src], out
+
+
 class DecodedColumn:
-    """Decoded chunk on the host: def/rep levels + dense values[:nn] (readValues outputs)."""
+    """Decoded chunk on the host: def/rep levels + dense values[:nn] (readValues outputs).
+
+    A chunk decoded with abi.COL_KEEP_DICT holds its `dictionary` (None when materialised):
+    values are then num_values little-endian int32 keys and value_width is 4; materialize()
+    gives the column as the decode without the flag lays it out."""
 
     def __init__(self, status, error_page, num_slots, num_values, value_width, def_levels, rep_levels, values,
-                 pages, offsets=None):
+                 pages, offsets=None, dictionary=None):
+        self.dictionary = dictionary
         self.status = status
         self.error_page = error_page
         self.num_slots = num_slots
@@ -154,6 +213,21 @@ class DecodedColumn:
         self.values = values          # fixed width: dense values; variable length: chars
         self.offsets = offsets        # variable length: int64[num_values + 1]
         self.pages = pages
+
+    def keys(self):
+        """The int32 dictionary keys of a column that kept its dictionary."""
+        return np.asarray(self.values, dtype=np.uint8).view("<i4")[:self.num_values]
+
+    def materialize(self):
+        """The host gather dictionary[keys]: this column in the layout of a decode without
+        abi.COL_KEEP_DICT (dense fixed-width bytes, or chars + int64 offsets; the dictionary's
+        nil_entry as zero bytes).  A materialised column (or a failed decode) is returned as it is."""
+        d = self.dictionary
+        if d is None or self.values is None:
+            return self
+        vals, offs = d.lookup(self.keys())
+        return DecodedColumn(self.status, self.error_page, self.num_slots, self.num_values, d.value_width,
+                             self.def_levels, self.rep_levels, vals, self.pages, offs)
 
 
 class GpuDecoder:
@@ -233,6 +307,17 @@ class GpuDecoder:
         if k < 0:
             raise PqgError(k, "pqg_get_pages")
         return [buf[i] for i in range(k)]
+
+    def dictionary(self, job_index):
+        """The dictionary of job `job_index` of the last decode, downloaded (a Dictionary).  The job
+        must carry abi.COL_KEEP_DICT (else PqgError INVALID_ARG); valid until the next decode."""
+        d = abi.Dictionary()
+        _check(self.L.pqg_get_dictionary(self.ctx, job_index, C.byref(d)), "pqg_get_dictionary")
+        vals = self.d2h(d.values, d.values_bytes) if d.values else np.zeros(0, np.uint8)
+        offs = None
+        if d.value_width == 0:
+            offs = self.d2h(d.offsets, (d.count + 1) * 8, np.int64) if d.offsets else np.zeros(1, np.int64)
+        return Dictionary(vals, offs, d.count, d.value_width, d.nil_entry, d.page)
 
     # ---- page checksums (PageHeader.crc)
     def set_verify_crc(self, on):
@@ -368,9 +453,10 @@ class GpuDecoder:
         _check(self.L.pqg_last_assemble_ms(self.ctx, C.byref(ms)), "pqg_last_assemble_ms")
         return ms.value
 
-    def download_nested(self, a, chars=None, physical_type=None, flags=0):
+    def download_nested(self, a, chars=None, physical_type=None, flags=0, dictionary=None):
         """The outputs of an assemble_nested call as a NestedColumn on the host
-        (`chars`: the decoded chars of a byte-array leaf, already downloaded)."""
+        (`chars`: the decoded chars of a byte-array leaf, already downloaded; `dictionary`:
+        the Dictionary of a leaf whose values are its keys)."""
         from .nested import NestedColumn
         levels = []
         for k in range(a.depth):
@@ -382,7 +468,8 @@ class GpuDecoder:
         vals = self.d2h(a.leaf_values, a.num_leaf * a.value_width) if a.leaf_values else None
         lo = self.d2h(a.leaf_offsets, (a.num_leaf + 1) * 8, np.int64) if a.leaf_offsets else None
         return NestedColumn(levels, lv, int(a.num_leaf), values=vals, value_width=a.value_width, chars=chars,
-                            leaf_offsets=lo, physical_type=physical_type, flags=flags, num_rows=int(a.num_rows))
+                            leaf_offsets=lo, physical_type=physical_type, flags=flags, num_rows=int(a.num_rows),
+                            dictionary=dictionary)
 
     def download(self, r, job_index=None):
         lv_def = self.d2h(r.def_levels, r.num_slots) if (r.def_levels and r.status == 0) else None
@@ -390,8 +477,10 @@ class GpuDecoder:
         vals = self.d2h(r.values, r.values_bytes) if r.status == 0 else None
         offs = self.d2h(r.offsets, (r.num_values + 1) * 8, np.int64) if (r.offsets and r.status == 0) else None
         pages = self.pages(job_index) if job_index is not None else None
+        # a job that kept its dictionary (abi.COL_KEEP_DICT): the keys, and the dictionary with them
+        keep = bool(r.col_flags & abi.COL_KEEP_DICT) and r.status == 0 and job_index is not None
         return DecodedColumn(r.status, r.error_page, r.num_slots, r.num_values, r.value_width, lv_def, lv_rep,
-                             vals, pages, offs)
+                             vals, pages, offs, dictionary=self.dictionary(job_index) if keep else None)
 
 
 def device_job(pf: ParquetFile, rg, col, dev_ptr_of_file):
@@ -475,8 +564,12 @@ def span_jobs(pf: ParquetFile, specs, dec, to_eof=()):
     return jobs, dev, total
 
 
-def decode_spans(pf: ParquetFile, specs, dec):
-    """span_jobs + pqg_decode_chunks for (rg, col) pairs.  A chunk whose decode
+def decode_spans(pf: ParquetFile, specs, dec, keep_dict=()):
+    """span_jobs + pqg_decode_chunks for (rg, col) pairs.  The chunks of the columns in
+    `keep_dict` (column indices) are decoded with abi.COL_KEEP_DICT; those that come back
+    NOT_DICT (a data page that is not dictionary encoded: a writer's fallback) are decoded
+    once more without it, in one second batch of the same jobs, so their results are
+    materialised (col_flags tells which).  A chunk whose decode
     ends in EOF / size mismatch while the file holds bytes past its uploaded
     range (a page overrunning TotalCompressedSize, which the reference still
     reads whole: chunk_reader.go:212-280) is decoded again with the bytes to the
@@ -484,7 +577,16 @@ def decode_spans(pf: ParquetFile, specs, dec):
     until the next decode on `dec`).  Returns (results, device buffer, bytes
     uploaded); the caller frees the buffer after using the outputs."""
     jobs, dev, nbytes = span_jobs(pf, specs, dec)
+    keep = {i for i, (_, c) in enumerate(specs) if c in keep_dict}
+    for i in keep:
+        jobs[i].col.flags |= abi.COL_KEEP_DICT
     res = dec.decode_jobs(jobs)
+    not_dict = {i for i in keep if res[i].status == abi.STATUS_CODES["NOT_DICT"]}
+    if not_dict:
+        keep -= not_dict
+        for i in not_dict:
+            jobs[i].col.flags &= ~abi.COL_KEEP_DICT
+        res = dec.decode_jobs(jobs)
     retry = set()
     for i, (job, r) in enumerate(zip(jobs, res)):
         m = pf.chunk_meta(*specs[i])
@@ -495,6 +597,8 @@ def decode_spans(pf: ParquetFile, specs, dec):
         dec.free(dev)
         jobs, dev, nb2 = span_jobs(pf, specs, dec, to_eof=retry)
         nbytes += nb2
+        for i in keep:
+            jobs[i].col.flags |= abi.COL_KEEP_DICT
         res = dec.decode_jobs(jobs)
     return res, dev, nbytes
 
@@ -506,17 +610,33 @@ class FileReader:
     bytes or a path (then only the footer and the selected chunks are read);
     each row group uploads only its selected chunks' bytes (span_jobs).
     `verify_crc`: check PageHeader.crc of the pages that carry one (GpuDecoder.set_verify_crc);
-    a page that fails makes the readers that raise PqgError raise it with code -18 (CRC)."""
+    a page that fails makes the readers that raise PqgError raise it with code -18 (CRC).
+    `read_dictionary`: dotted paths (as `columns`: a path or a prefix) of columns to keep
+    dictionary encoded, as pyarrow's read_dictionary= does: read_row_group, decode_row_groups and
+    read_row_group_nested decode their chunks with abi.COL_KEEP_DICT (int32 keys plus a
+    Dictionary instead of values).  A chunk with a data page that is not dictionary encoded is
+    decoded again without the flag and comes back materialised (dictionary None).  BOOLEAN
+    columns are never flagged; next_row ignores the option, rows need values."""
 
-    def __init__(self, source, *columns, device=0, decoder=None, verify_crc=False):
+    def __init__(self, source, *columns, device=0, decoder=None, verify_crc=False, read_dictionary=()):
         self.file = ParquetFile.open(source) if isinstance(source, (str, os.PathLike)) else ParquetFile(source)
         self.dec = decoder or GpuDecoder(device)
         if verify_crc:
             self.dec.set_verify_crc(True)
         self.selected = self._select(columns)
+        self.keep_dict = frozenset(
+            i for i in (self._select(tuple(read_dictionary)) if read_dictionary else [])
+            if i in self.selected and self.file.columns[i].desc.physical_type != abi.BOOLEAN)
         self.row_group_position = 0
         self.uploaded_bytes = 0   # H2D bytes so far (projection pushdown check)
         self._rows = None         # NextRow state (pqgpu.rows.RowReader)
+        self._held = None         # chunk bytes decode_row_groups left on the device (in-place dictionaries)
+
+    def _release(self):
+        """Free the chunk bytes the last decode_row_groups kept for its dictionaries."""
+        if self._held is not None:
+            self.dec.free(self._held)
+            self._held = None
 
     def _select(self, columns):
         if not columns:
@@ -537,21 +657,32 @@ class FileReader:
     def decode_row_groups(self, rgs):
         """readRowGroup (chunk_reader.go:404-431) for the selected columns of
         every row group in `rgs`, one batched decode: [(rg, col, ChunkResult)]
-        with device outputs (valid until the next decode on the decoder)."""
+        with device outputs (valid until the next decode on the decoder).
+        Result i is job i of that decode: for one whose col_flags carry
+        abi.COL_KEEP_DICT, self.dec.dictionary(i) is its dictionary.  A
+        fixed-width dictionary of an uncompressed chunk is handed out in place,
+        inside the uploaded chunk bytes, so when any chunk kept its dictionary
+        the upload stays on the device until this reader's next decode (any of
+        its read / decode methods) or close(); otherwise it is freed here."""
+        self._release()
         specs = [(rg, c) for rg in rgs for c in self.selected]
         if not specs:
             return []
-        res, dev, nbytes = decode_spans(self.file, specs, self.dec)
+        res, dev, nbytes = decode_spans(self.file, specs, self.dec, self.keep_dict)
         self.uploaded_bytes += nbytes
-        self.dec.free(dev)
+        if any(r.col_flags & abi.COL_KEEP_DICT for r in res):
+            self._held = dev
+        else:
+            self.dec.free(dev)
         return [(rg, c, r) for (rg, c), r in zip(specs, res)]
 
     def read_row_group(self, rg):
         """One row group's selected columns, downloaded: {path: DecodedColumn}."""
+        self._release()
         specs = [(rg, c) for c in self.selected]
         if not specs:
             return {}
-        res, dev, nbytes = decode_spans(self.file, specs, self.dec)
+        res, dev, nbytes = decode_spans(self.file, specs, self.dec, self.keep_dict)
         self.uploaded_bytes += nbytes
         try:
             return {self.file.columns[c].path.decode(): self.dec.download(r, i)
@@ -567,6 +698,7 @@ class FileReader:
         Arrow buffers are downloaded: no level leaves the device.  A leaf under
         more than abi.MAX_LIST_DEPTH lists raises PqgError(UNSUPPORTED)."""
         from .nested import leaf_thresholds
+        self._release()
         specs = [(rg, c) for c in self.selected]
         if not specs:
             return {}
@@ -577,21 +709,23 @@ class FileReader:
                 raise PqgError(abi.STATUS_CODES["UNSUPPORTED"], "column %s: %d list depths (at most %d)"
                                % (self.file.columns[c].path.decode(), len(ed), abi.MAX_LIST_DEPTH))
             thr[c] = (ld, ed)
-        res, dev, nbytes = decode_spans(self.file, specs, self.dec)
+        res, dev, nbytes = decode_spans(self.file, specs, self.dec, self.keep_dict)
         self.uploaded_bytes += nbytes
         out = {}
         try:
-            for (_, c), r in zip(specs, res):
+            for i, ((_, c), r) in enumerate(zip(specs, res)):
                 path = self.file.columns[c].path.decode()
                 if r.status != 0:
                     raise PqgError(r.status, "column %s of row group %d" % (path, rg))
                 desc = self.file.columns[c].desc
                 ld, ed = thr[c]
+                # a leaf that kept its dictionary goes through as the 4-byte fixed-width leaf its keys are
+                dic = self.dec.dictionary(i) if r.col_flags & abi.COL_KEEP_DICT else None
                 a = self.dec.assemble_nested(r.def_levels, r.rep_levels, r.values, r.num_slots, desc.max_def, ld, ed,
                                              value_width=r.value_width, value_offsets_ptr=r.offsets)
                 try:
                     chars = self.dec.d2h(r.values, r.values_bytes) if r.offsets else None
-                    out[path] = self.dec.download_nested(a, chars, desc.physical_type, desc.flags)
+                    out[path] = self.dec.download_nested(a, chars, desc.physical_type, desc.flags, dic)
                 finally:
                     self.dec.free_nested(a)
             return out
@@ -608,6 +742,7 @@ class FileReader:
         return self._rows.next_row()
 
     def _decode_for_rows(self, rg):
+        self._release()
         specs = [(rg, c) for c in self.selected]
         if not specs:
             return {}
@@ -619,4 +754,4 @@ class FileReader:
             self.dec.free(dev)
 
     def close(self):
-        pass
+        self._release()
