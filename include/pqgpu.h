@@ -529,6 +529,94 @@ int pqg_assemble_nested(pqg_ctx* ctx, pqg_nested_args* args);
  * launches (the count read-back and host syncs excluded). */
 int pqg_last_assemble_ms(pqg_ctx* ctx, float* ms);
 
+/* ---- K9s: row predicates and row selection (beyond the reference, which has no
+ * filter: FileReader returns every row of a row group) ------------------------
+ * Rows are those of a FLAT column (max_rep == 0: num_rows == num_slots).  Row i is
+ * null when def[i] < max_def (def_levels NULL: no row is null), and dense value r
+ * belongs to the r-th non-null row.  All array pointers are DEVICE pointers (e.g. a
+ * pqg_chunk_result's); both entries enqueue on the ctx stream and wait, write no
+ * output when they fail, and do nothing when num_rows == 0 (counts 0). */
+enum {
+  PQG_OP_EQ = 0, PQG_OP_NE = 1, PQG_OP_LT = 2, PQG_OP_LE = 3, PQG_OP_GT = 4, PQG_OP_GE = 5,
+  PQG_OP_IS_NULL = 6, PQG_OP_NOT_NULL = 7
+};
+enum {
+  PQG_COMBINE_SET = 0,  /* bitmap  = result          */
+  PQG_COMBINE_AND = 1,  /* bitmap &= result          */
+  PQG_COMBINE_OR = 2    /* bitmap |= result          */
+};
+
+/* pqg_filter: one comparison `column op literal` into a row bitmap: one bit per row,
+ * LSB first, 4 * ceil(num_rows / 32) bytes, read (AND / OR) and written as whole
+ * dwords.  Bits at and past num_rows are zero after every call, whatever the operator
+ * or mode.  A null row fails every comparison, NE included, and passes only IS_NULL.
+ * Comparison by col.physical_type: INT32 / INT64 signed, or unsigned with
+ * PQG_COL_UNSIGNED in col.flags; FLOAT / DOUBLE IEEE (NaN, as value or as literal,
+ * fails everything but NE, which it passes; -0.0 == 0.0); BOOLEAN one byte, 0 < 1;
+ * BYTE_ARRAY and FIXED_LEN_BYTE_ARRAY (type_length >= 1) unsigned lexicographic over
+ * the bytes (a proper prefix sorts first, the empty string lowest); INT96, and FLBA with
+ * type_length < 1, are PQG_ERR_UNSUPPORTED, and so is col.max_rep > 0.  `literal` is
+ * HOST memory in the column's physical little-endian layout (ignored by IS_NULL /
+ * NOT_NULL): a length other than 4 / 8 / 1 / type_length for a fixed-width type is
+ * PQG_ERR_INVALID_ARG.  Fixed-width values must be naturally aligned (4- and 8-byte
+ * types; a chunk result's are); a dictionary's entries need no alignment.
+ * Kept dictionaries: for a column decoded with PQG_COL_KEEP_DICT pass its
+ * pqg_dictionary; `values` are then the int32 keys.  The comparison runs once per
+ * dictionary entry (a nil_entry, or an entry the page does not hold, reads as zero
+ * bytes) and a row passes when its key's entry does; a key outside [0, count) fails.
+ * A non-null row whose rank is at or past num_values fails every operator but IS_NULL. */
+typedef struct pqg_filter_args {
+  const uint8_t* def_levels;   /* num_rows bytes, or NULL                               */
+  const uint8_t* values;       /* dense values / chars, or int32 keys with `dictionary` */
+  const int64_t* offsets;      /* BYTE_ARRAY without `dictionary`: num_values + 1       */
+  int64_t num_rows;
+  int64_t num_values;          /* dense values at `values`                              */
+  int64_t values_bytes;        /* bytes at `values` (chars for byte arrays)             */
+  pqg_column_desc col;         /* physical_type, type_length, max_def, max_rep, flags   */
+  int32_t op;                  /* PQG_OP_*                                              */
+  int32_t combine;             /* PQG_COMBINE_*                                         */
+  const uint8_t* literal;      /* HOST                                                  */
+  int64_t literal_len;
+  const pqg_dictionary* dictionary; /* HOST struct of DEVICE pointers, or NULL          */
+  uint8_t* bitmap;             /* in (AND / OR) and out                                 */
+  int64_t num_selected;        /* out: popcount of the bitmap after combining           */
+  int64_t num_valid;           /* out: non-null rows                                    */
+} pqg_filter_args;
+int pqg_filter(pqg_ctx* ctx, pqg_filter_args* args);
+
+/* pqg_select: compact one column by a row bitmap (pqg_filter's layout; bits at and past
+ * num_rows are ignored) into the chunk-result layout, so that pqg_assemble*, a download
+ * or a dictionary lookup work on the filtered column unchanged: the selected rows' def
+ * levels, the dense values of the selected non-null rows (any value_width >= 1), and for
+ * byte arrays (value_width 0) int64 offsets rebased to 0 (values_out + 1 of them) plus
+ * the selected chars back to back.  A column of int32 dictionary keys is a 4-byte
+ * column; its dictionary is untouched.  Outputs are caller-allocated; each may be NULL
+ * (not written), and with all three NULL the call only counts.  They never exceed the
+ * inputs: num_rows bytes, values_bytes bytes and num_values + 1 offsets always suffice,
+ * and a counting call gives the exact sizes.  Inputs and outputs must not overlap. */
+typedef struct pqg_select_args {
+  const uint8_t* bitmap;       /* 4 * ceil(num_rows / 32) bytes                          */
+  const uint8_t* def_levels;   /* num_rows bytes, or NULL                                */
+  const uint8_t* values;
+  const int64_t* offsets;      /* byte arrays: num_values + 1                            */
+  int64_t num_rows;
+  int64_t num_values;
+  int64_t values_bytes;
+  int32_t max_def;
+  int32_t value_width;         /* bytes per value; 0 = byte arrays                       */
+  uint8_t* out_def_levels;     /* rows_out bytes                                         */
+  uint8_t* out_values;         /* values_out x value_width, or bytes_out chars           */
+  int64_t* out_offsets;        /* byte arrays: values_out + 1                            */
+  int64_t rows_out;            /* out: selected rows                                     */
+  int64_t values_out;          /* out: selected non-null rows                            */
+  int64_t bytes_out;           /* out: value bytes (chars for byte arrays)               */
+} pqg_select_args;
+int pqg_select(pqg_ctx* ctx, pqg_select_args* args);
+
+/* Device time (ms) of the kernels of the last pqg_filter / pqg_select call (an event
+ * pair on the ctx stream; the literal upload and the count read-back excluded). */
+int pqg_last_filter_ms(pqg_ctx* ctx, float* ms);
+
 /* ---- host-side planner: footer / schema (file_meta.go:14-62, schema.go) --- */
 typedef struct pqg_file pqg_file;
 
@@ -566,6 +654,19 @@ int64_t pqg_file_num_rows(const pqg_file* f);
 int pqg_file_column(const pqg_file* f, int col, pqg_column_info* out);
 int pqg_file_chunk(const pqg_file* f, int row_group, int col, pqg_chunk_meta* out);
 int64_t pqg_file_row_group_rows(const pqg_file* f, int row_group);
+
+/* ColumnMetaData.statistics (field 12) of a chunk: null_count (3), max_value (5) and
+ * min_value (6) only.  The deprecated max / min (1, 2) are skipped: their sort order is
+ * undefined for unsigned types and byte arrays.  Values are the column's physical
+ * little-endian bytes, as the file stores them; the pointers stay valid until
+ * pqg_file_close.  A file in which any statistics struct does not parse reports no
+ * statistics for any chunk (and opens as it did before). */
+typedef struct pqg_chunk_stats {
+  const uint8_t *min_value, *max_value;  /* owned by the pqg_file; NULL = absent */
+  int32_t min_len, max_len;
+  int64_t null_count;                    /* -1 = absent */
+} pqg_chunk_stats;
+int pqg_file_chunk_stats(const pqg_file* f, int row_group, int col, pqg_chunk_stats* out);
 
 /* The schema tree below the root, depth first (makeSchema / readGroupSchema
  * schema.go:789-894, 996-1025): what NextRow's row assembly walks

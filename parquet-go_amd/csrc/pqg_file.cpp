@@ -36,6 +36,10 @@ struct ChunkM {
   bool has_meta = false, has_path = false, has_dict = false;
   int32_t type = 0, codec = 0;
   int64_t num_values = 0, tus = 0, tcs = 0, data_off = 0, dict_off = 0;
+  // Statistics (field 12): null_count, max_value, min_value
+  bool has_nulls = false, has_min = false, has_max = false;
+  int64_t null_count = 0;
+  std::string min_value, max_value;
 };
 
 struct Leaf {
@@ -47,6 +51,7 @@ struct Parser {
   Compact<MemSrc> c;
   SkipFrame frames[kMaxFrames];
   int16_t last[kMaxLast];
+  bool stats_bad = false;  // a Statistics struct that did not parse: the file reports none
   explicit Parser(const uint8_t* p, int64_t n) {
     c.src = MemSrc{p, n};
     c.pos = 0;
@@ -146,9 +151,49 @@ struct Parser {
         case 7: if (t == T_I64) { if (c.i64(&w)) return -1; m->tcs = w; return 1; } break;
         case 9: if (t == T_I64) { if (c.i64(&w)) return -1; m->data_off = w; return 1; } break;
         case 11: if (t == T_I64) { if (c.i64(&w)) return -1; m->dict_off = w; m->has_dict = true; return 1; } break;
+        case 12:
+          if (t == T_STRUCT) {
+            // skipped exactly as an unknown field is, then read from its own bytes: a
+            // statistics struct never changes whether or how the footer parses
+            const int64_t s0 = c.pos;
+            if (c.skip(t, 64)) return -1;
+            if (!stats(c.src.p + s0, c.pos - s0, m)) stats_bad = true;
+            return 1;
+          }
+          break;
       }
       return 0;
     });
+  }
+  // Statistics: 3 null_count, 5 max_value, 6 min_value; the deprecated max / min (1, 2)
+  // and everything else are skipped
+  static bool stats(const uint8_t* p, int64_t n, ChunkM* m) {
+    Parser q(p, n);
+    ChunkM s;
+    const bool ok = q.fields([&](int t, int id) -> int {
+      if (id == 3 && t == T_I64) {
+        if (q.c.i64(&s.null_count)) return -1;
+        s.has_nulls = true;
+        return 1;
+      }
+      if (id == 5 && t == T_STRING) {
+        s.has_max = true;
+        return q.str(&s.max_value) ? 1 : -1;
+      }
+      if (id == 6 && t == T_STRING) {
+        s.has_min = true;
+        return q.str(&s.min_value) ? 1 : -1;
+      }
+      return 0;
+    });
+    if (!ok || q.c.pos != n) return false;
+    m->has_nulls = s.has_nulls;
+    m->has_min = s.has_min;
+    m->has_max = s.has_max;
+    m->null_count = s.null_count;
+    m->min_value = s.min_value;
+    m->max_value = s.max_value;
+    return true;
   }
   bool chunk(ChunkM* m) {
     return fields([&](int t, int id) -> int {
@@ -180,6 +225,7 @@ struct pqg_file {
   std::vector<std::vector<ChunkM>> rgs;
   std::vector<int64_t> rg_rows;
   int64_t num_rows = 0;
+  bool stats_bad = false;
 };
 
 namespace {
@@ -313,6 +359,7 @@ static int open_footer(const uint8_t* footer, int32_t fl, pqg_file** out) {
   f->rgs = rgs;
   f->rg_rows = rg_rows;
   f->num_rows = num_rows;
+  f->stats_bad = P.stats_bad;
   *out = f;
   return PQG_OK;
 }
@@ -371,6 +418,29 @@ int pqg_file_chunk(const pqg_file* f, int rg, int col, pqg_chunk_meta* out) {
   out->has_dict_page_offset = m.has_dict ? 1 : 0;
   out->codec = m.codec;
   out->type = m.type;
+  return PQG_OK;
+}
+
+// ColumnMetaData.statistics of the chunk pqg_file_chunk describes.
+int pqg_file_chunk_stats(const pqg_file* f, int rg, int col, pqg_chunk_stats* out) {
+  if (!f || !out || rg < 0 || rg >= (int)f->rgs.size() || col < 0 || col >= (int)f->leaves.size())
+    return PQG_ERR_INVALID_ARG;
+  memset(out, 0, sizeof(*out));
+  out->null_count = -1;
+  const std::vector<ChunkM>& cols = f->rgs[(size_t)rg];
+  if ((int)cols.size() <= col) return PQG_ERR_METADATA;
+  const ChunkM& m = cols[(size_t)col];
+  if (m.has_path || !m.has_meta) return PQG_ERR_METADATA;
+  if (f->stats_bad) return PQG_OK;
+  if (m.has_min) {
+    out->min_value = (const uint8_t*)m.min_value.data();
+    out->min_len = (int32_t)m.min_value.size();
+  }
+  if (m.has_max) {
+    out->max_value = (const uint8_t*)m.max_value.data();
+    out->max_len = (int32_t)m.max_value.size();
+  }
+  if (m.has_nulls) out->null_count = m.null_count;
   return PQG_OK;
 }
 

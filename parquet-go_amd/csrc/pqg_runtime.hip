@@ -19,6 +19,7 @@
 #include "../../include/pqgpu.h"
 #include "pqg_common.h"
 #include "pqg_crc.h"
+#include "pqg_filter.h"
 #include "pqg_lz4.h"
 #include "pqg_zstd.h"
 
@@ -29,6 +30,9 @@ int list_write_launch(hipStream_t s, const pqg_list_args* a, int64_t* seg_scratc
 int nested_count_launch(hipStream_t s, const pqg_nested_args* a, int64_t* seg_scratch, int64_t* tot);  // pqg_assemble.hip
 int nested_write_launch(hipStream_t s, const pqg_nested_args* a, int64_t* seg_scratch, const int64_t* tot);  // pqg_assemble.hip
 int pack_levels_launch(hipStream_t s, const uint8_t* levels, int64_t n, int bw, uint8_t* packed);     // pqg_assemble.hip
+int filter_launch(hipStream_t s, const flt::Pred& p, const flt::Col& c, const pqg_dictionary* dict, uint32_t* ebits,
+                  uint8_t* bitmap, int64_t n, int mode, bool lds, int64_t* seg, int64_t* tot);            // pqg_filter.hip
+int select_launch(hipStream_t s, const flt::Sel& a, int64_t* seg, int64_t* tot);                          // pqg_filter.hip
 }
 
 namespace pqg {
@@ -251,6 +255,10 @@ struct pqg_ctx {
   DevBuf streams, runs, blks;  // K3 hybrid run tables
   DevBuf cand_list, vlists;
   DevBuf asm_seg;  // K8 per-segment counts + totals
+  DevBuf flt_buf;  // K9s: per-segment counts + totals, the literal's bytes, the dictionary-entry bitmap
+  hipEvent_t ev_flt[2];
+  float flt_ms = 0.f;    // device time of the last pqg_filter / pqg_select
+  bool flt_lds = true;   // entry bitmaps of up to flt::kLdsEntries entries are staged in LDS (PQG_FILTER_LDS=0: read through L2)
   DevBuf offs_arena, doffs_arena;  // K7: value offsets (int64), dictionary record starts
   DevBuf aoffs_arena, dchars_arena;  // K4i: byte-array dictionaries in Arrow layout (k_dict_export): offsets (laid out as
                                      // doffs_arena), chars
@@ -344,6 +352,8 @@ int pqg_ctx_create(int device, pqg_ctx** out) {
   for (auto& e : c->ev) hipEventCreate(&e);
   for (auto& e : c->ev_k8) hipEventCreate(&e);
   for (auto& e : c->ev_crc) hipEventCreate(&e);
+  for (auto& e : c->ev_flt) hipEventCreate(&e);
+  if (const char* e = getenv("PQG_FILTER_LDS")) c->flt_lds = atoi(e) != 0;
   if (const char* e = getenv("PQG_VERIFY_CRC")) c->verify_crc = atoi(e) != 0;
   if (const char* e = getenv("PQG_CRC_TILE_CAP")) c->crc_cap_limit = atoi(e) > 0 ? atoi(e) : 0;
   if (const char* e = getenv("PQG_DICT4")) c->dict4 = atoi(e) != 0;
@@ -401,13 +411,14 @@ void pqg_ctx_destroy(pqg_ctx* c) {
   for (auto& e : c->ev) hipEventDestroy(e);
   for (auto& e : c->ev_k8) hipEventDestroy(e);
   for (auto& e : c->ev_crc) hipEventDestroy(e);
+  for (auto& e : c->ev_flt) hipEventDestroy(e);
   for (DevBuf* b : {&c->jobs, &c->pages, &c->list, &c->counters, &c->def_arena, &c->rep_arena, &c->value_arena,
                     &c->scratch, &c->streams, &c->runs, &c->blks, &c->cand_list, &c->vlists, &c->tile_count, &c->tile_okc, &c->tile_off, &c->tile_okoff, &c->cand_pos, &c->cands, &c->succ, &c->idx2slot,
                     &c->ok2slot, &c->order, &c->asm_seg, &c->offs_arena, &c->doffs_arena, &c->page_stage,
                     &c->blk_src, &c->blk_dst, &c->blk_meta, &c->tile_job, &c->sn_subs, &c->sn_segpage, &c->sn_F,
                     &c->blk_subs, &c->blk_segpage, &c->blk_F, &c->vrecs, &c->parts, &c->lev_long, &c->lev_pieces,
                     &c->walk_long, &c->nn_sums, &c->nn_jobs, &c->zstd_ws, &c->crc_recs, &c->crc_tiles, &c->crc_raws,
-                    &c->crc_one, &c->aoffs_arena, &c->dchars_arena})
+                    &c->crc_one, &c->aoffs_arena, &c->dchars_arena, &c->flt_buf})
     b->release();
   if (c->h_jobs) hipHostFree(c->h_jobs);
   hipStreamDestroy(c->stream);
@@ -1080,6 +1091,156 @@ int pqg_assemble_nested(pqg_ctx* c, pqg_nested_args* a) {
 int pqg_last_assemble_ms(pqg_ctx* c, float* ms) {
   if (!c || !ms) return PQG_ERR_INVALID_ARG;
   *ms = c->k8_ms;
+  return PQG_OK;
+}
+
+// K9s: `column op literal` per row into a row bitmap (pqg_filter.hip).
+int pqg_filter(pqg_ctx* c, pqg_filter_args* a) {
+  if (!c || !a) return PQG_ERR_INVALID_ARG;
+  if (a->num_rows < 0 || a->num_values < 0 || a->values_bytes < 0 || a->col.max_def < 0 || a->col.max_def > 255 ||
+      a->op < PQG_OP_EQ || a->op > PQG_OP_NOT_NULL || a->combine < PQG_COMBINE_SET || a->combine > PQG_COMBINE_OR)
+    return PQG_ERR_INVALID_ARG;
+  if (a->col.max_rep > 0) return PQG_ERR_UNSUPPORTED;
+  const int type = a->col.physical_type;
+  const bool uns = (a->col.flags & PQG_COL_UNSIGNED) != 0;
+  flt::Pred p;
+  memset(&p, 0, sizeof(p));
+  p.op = a->op;
+  switch (type) {
+    case PQG_BOOLEAN: p.kind = flt::K_U8; p.width = 1; break;
+    case PQG_INT32: p.kind = uns ? flt::K_U32 : flt::K_I32; p.width = 4; break;
+    case PQG_INT64: p.kind = uns ? flt::K_U64 : flt::K_I64; p.width = 8; break;
+    case PQG_FLOAT: p.kind = flt::K_F32; p.width = 4; break;
+    case PQG_DOUBLE: p.kind = flt::K_F64; p.width = 8; break;
+    case PQG_BYTE_ARRAY: p.kind = flt::K_BYTES; p.width = 0; break;
+    case PQG_FIXED_LEN_BYTE_ARRAY:
+      if (a->col.type_length < 1) return PQG_ERR_UNSUPPORTED;
+      p.kind = flt::K_FLBA;
+      p.width = a->col.type_length;
+      break;
+    default: return PQG_ERR_UNSUPPORTED;  // INT96
+  }
+  const bool cmp = a->op != PQG_OP_IS_NULL && a->op != PQG_OP_NOT_NULL;
+  const bool bytes = p.kind == flt::K_BYTES || p.kind == flt::K_FLBA;
+  if (cmp) {
+    if (a->literal_len < 0 || (a->literal_len > 0 && !a->literal)) return PQG_ERR_INVALID_ARG;
+    if (p.kind != flt::K_BYTES && a->literal_len != p.width) return PQG_ERR_INVALID_ARG;
+    if (!bytes) memcpy(&p.lit, a->literal, (size_t)p.width);  // little endian
+    p.lit_len = a->literal_len;
+  }
+  const pqg_dictionary* d = a->dictionary;
+  const int64_t n = a->num_rows;
+  if (n > 0) {
+    if (!a->bitmap) return PQG_ERR_INVALID_ARG;
+    if (a->num_values > 0 && !a->values) return PQG_ERR_INVALID_ARG;
+    if (d) {
+      if (d->count < 0 || d->value_width != p.width || a->values_bytes < 4 * a->num_values ||
+          ((uintptr_t)a->values & 3) || (d->count > 0 && (!d->values && d->values_bytes > 0)) ||
+          (p.kind == flt::K_BYTES && d->count > 0 && !d->offsets))
+        return PQG_ERR_INVALID_ARG;
+    } else {
+      if (p.kind == flt::K_BYTES ? (a->num_values > 0 && !a->offsets) : a->values_bytes < (int64_t)p.width * a->num_values)
+        return PQG_ERR_INVALID_ARG;
+      if ((p.width == 4 || p.width == 8) && !bytes && ((uintptr_t)a->values & (uintptr_t)(p.width - 1)))
+        return PQG_ERR_INVALID_ARG;
+    }
+  }
+  a->num_selected = 0;
+  a->num_valid = 0;
+  c->flt_ms = 0.f;
+  if (n == 0) return PQG_OK;
+  hipSetDevice(c->device);
+  const int64_t nseg = (n + flt::kSeg - 1) / flt::kSeg;
+  const size_t o_tot = sizeof(int64_t) * (size_t)nseg, o_lit = o_tot + 2 * sizeof(int64_t);
+  const size_t o_eb = o_lit + (((size_t)p.lit_len + 7) & ~(size_t)7);
+  const size_t eb_bytes = d ? (size_t)((d->count + 31) / 32) * 4 : 0;
+  if (c->flt_buf.grow(o_eb + eb_bytes + 8)) return PQG_ERR_HIP;
+  uint8_t* base = (uint8_t*)c->flt_buf.p;
+  int64_t* seg = (int64_t*)base;
+  int64_t* tot = (int64_t*)(base + o_tot);
+  if (cmp && bytes && p.lit_len > 0 &&
+      hipMemcpyAsync(base + o_lit, a->literal, (size_t)p.lit_len, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+    return PQG_ERR_HIP;
+  p.lit_bytes = (uintptr_t)(base + o_lit);
+  flt::Col col;
+  memset(&col, 0, sizeof(col));
+  col.def = a->col.max_def > 0 ? (uintptr_t)a->def_levels : 0;
+  col.values = (uintptr_t)a->values;
+  col.offsets = (uintptr_t)a->offsets;
+  col.num_values = a->num_values;
+  col.values_bytes = a->values_bytes;
+  col.max_def = a->col.max_def;
+  col.dict = d != nullptr;
+  col.ebits = (uintptr_t)(base + o_eb);
+  col.dict_count = d ? d->count : 0;
+  hipEventRecord(c->ev_flt[0], c->stream);
+  int e = pqg::filter_launch(c->stream, p, col, d, (uint32_t*)(base + o_eb), a->bitmap, n, a->combine, c->flt_lds, seg,
+                             tot);
+  if (e) return e;
+  hipEventRecord(c->ev_flt[1], c->stream);
+  int64_t h[2] = {0, 0};
+  if (hipMemcpyAsync(h, tot, sizeof(h), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+      hipStreamSynchronize(c->stream) != hipSuccess)
+    return PQG_ERR_HIP;
+  hipEventElapsedTime(&c->flt_ms, c->ev_flt[0], c->ev_flt[1]);
+  a->num_valid = col.def ? h[0] : n;
+  a->num_selected = h[1];
+  return PQG_OK;
+}
+
+// K9s: compact one column by a row bitmap into the chunk-result layout (pqg_filter.hip).
+int pqg_select(pqg_ctx* c, pqg_select_args* a) {
+  if (!c || !a || a->num_rows < 0 || a->num_values < 0 || a->values_bytes < 0 || a->max_def < 0 || a->max_def > 255 ||
+      a->value_width < 0)
+    return PQG_ERR_INVALID_ARG;
+  const int64_t n = a->num_rows;
+  const int w = a->value_width;
+  if (n > 0) {
+    if (!a->bitmap || (a->num_values > 0 && !a->values)) return PQG_ERR_INVALID_ARG;
+    if (w == 0 ? (a->num_values > 0 && !a->offsets) : a->values_bytes < (int64_t)w * a->num_values)
+      return PQG_ERR_INVALID_ARG;
+    if (w == 0 && a->out_offsets && ((uintptr_t)a->out_offsets & 7)) return PQG_ERR_INVALID_ARG;
+  }
+  a->rows_out = a->values_out = a->bytes_out = 0;
+  c->flt_ms = 0.f;
+  if (n == 0) return PQG_OK;
+  hipSetDevice(c->device);
+  const int64_t nseg = (n + flt::kSeg - 1) / flt::kSeg;
+  if (c->flt_buf.grow(sizeof(int64_t) * (size_t)(4 * nseg + 4))) return PQG_ERR_HIP;
+  int64_t* seg = (int64_t*)c->flt_buf.p;
+  int64_t* tot = seg + 4 * nseg;
+  flt::Sel s;
+  memset(&s, 0, sizeof(s));
+  s.bitmap = (uintptr_t)a->bitmap;
+  s.def = a->max_def > 0 ? (uintptr_t)a->def_levels : 0;
+  s.values = (uintptr_t)a->values;
+  s.offsets = (uintptr_t)a->offsets;
+  s.out_def = (uintptr_t)a->out_def_levels;
+  s.out_values = (uintptr_t)a->out_values;
+  s.out_offsets = w == 0 ? (uintptr_t)a->out_offsets : 0;
+  s.n = n;
+  s.num_values = a->num_values;
+  s.values_bytes = a->values_bytes;
+  s.max_def = a->max_def;
+  s.width = w;
+  hipEventRecord(c->ev_flt[0], c->stream);
+  int e = pqg::select_launch(c->stream, s, seg, tot);
+  if (e) return e;
+  hipEventRecord(c->ev_flt[1], c->stream);
+  int64_t h[4] = {0, 0, 0, 0};
+  if (hipMemcpyAsync(h, tot, sizeof(h), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+      hipStreamSynchronize(c->stream) != hipSuccess)
+    return PQG_ERR_HIP;
+  hipEventElapsedTime(&c->flt_ms, c->ev_flt[0], c->ev_flt[1]);
+  a->rows_out = h[1];
+  a->values_out = h[2];
+  a->bytes_out = w == 0 ? h[3] : h[2] * w;
+  return PQG_OK;
+}
+
+int pqg_last_filter_ms(pqg_ctx* c, float* ms) {
+  if (!c || !ms) return PQG_ERR_INVALID_ARG;
+  *ms = c->flt_ms;
   return PQG_OK;
 }
 

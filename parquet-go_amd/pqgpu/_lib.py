@@ -62,6 +62,10 @@ def lib():
         "pqg_file_chunk": ([P, I, I, C.POINTER(abi.ChunkMeta)], I),
         "pqg_file_num_schema_nodes": ([P], I),
         "pqg_file_schema_node": ([P, I, C.POINTER(abi.SchemaNode)], I),
+        "pqg_file_chunk_stats": ([P, I, I, C.POINTER(abi.ChunkStats)], I),
+        "pqg_filter": ([P, C.POINTER(abi.FilterArgs)], I),
+        "pqg_select": ([P, C.POINTER(abi.SelectArgs)], I),
+        "pqg_last_filter_ms": ([P, C.POINTER(C.c_float)], I),
     }
     for name, (args, res) in sig.items():
         # a library named by PQG_LIB may be an older build (A/B runs against a parent's library):
@@ -83,5 +87,5 @@ EXPORTED = [
     "pqg_file_close", "pqg_set_verify_crc", "pqg_get_page_crcs", "pqg_crc32", "pqg_last_crc_ms",
     "pqg_file_num_columns", "pqg_file_num_row_groups", "pqg_file_num_rows", "pqg_file_row_group_rows",
     "pqg_file_column", "pqg_file_chunk", "pqg_file_num_schema_nodes", "pqg_file_schema_node",
-    "pqg_get_dictionary",
+    "pqg_get_dictionary", "pqg_file_chunk_stats", "pqg_filter", "pqg_select", "pqg_last_filter_ms",
 ]

@@ -214,5 +214,34 @@ class NestedArgs(C.Structure):
                 ("num_rows", C.c_int64), ("num_leaf", C.c_int64), ("num_valid", C.c_int64)]
 
 
+class ChunkStats(C.Structure):
+    """pqg_chunk_stats (include/pqgpu.h): ColumnMetaData.statistics of one chunk."""
+    _fields_ = [("min_value", C.c_void_p), ("max_value", C.c_void_p), ("min_len", C.c_int32),
+                ("max_len", C.c_int32), ("null_count", C.c_int64)]
+
+
+# pqg_filter operators and combine modes
+OP_EQ, OP_NE, OP_LT, OP_LE, OP_GT, OP_GE, OP_IS_NULL, OP_NOT_NULL = range(8)
+COMBINE_SET, COMBINE_AND, COMBINE_OR = range(3)
+
+
+class FilterArgs(C.Structure):
+    """pqg_filter_args (include/pqgpu.h, K9s)."""
+    _fields_ = [("def_levels", C.c_void_p), ("values", C.c_void_p), ("offsets", C.c_void_p),
+                ("num_rows", C.c_int64), ("num_values", C.c_int64), ("values_bytes", C.c_int64),
+                ("col", ColumnDesc), ("op", C.c_int32), ("combine", C.c_int32),
+                ("literal", C.c_void_p), ("literal_len", C.c_int64), ("dictionary", C.POINTER(Dictionary)),
+                ("bitmap", C.c_void_p), ("num_selected", C.c_int64), ("num_valid", C.c_int64)]
+
+
+class SelectArgs(C.Structure):
+    """pqg_select_args (include/pqgpu.h, K9s)."""
+    _fields_ = [("bitmap", C.c_void_p), ("def_levels", C.c_void_p), ("values", C.c_void_p), ("offsets", C.c_void_p),
+                ("num_rows", C.c_int64), ("num_values", C.c_int64), ("values_bytes", C.c_int64),
+                ("max_def", C.c_int32), ("value_width", C.c_int32),
+                ("out_def_levels", C.c_void_p), ("out_values", C.c_void_p), ("out_offsets", C.c_void_p),
+                ("rows_out", C.c_int64), ("values_out", C.c_int64), ("bytes_out", C.c_int64)]
+
+
 def status_name(code):
     return STATUS.get(int(code), str(code))

@@ -116,6 +116,15 @@ class ParquetFile:
         _check(lib().pqg_file_chunk(self._h, rg, col, C.byref(m)), "pqg_file_chunk")
         return m
 
+    def chunk_stats(self, rg, col):
+        """ColumnMetaData.statistics of a chunk: (min_value, max_value, null_count), the values
+        as the physical little-endian bytes the footer holds, None / -1 for what is absent."""
+        st = abi.ChunkStats()
+        _check(lib().pqg_file_chunk_stats(self._h, rg, col, C.byref(st)), "pqg_file_chunk_stats")
+        lo = C.string_at(st.min_value, st.min_len) if st.min_value else None
+        hi = C.string_at(st.max_value, st.max_len) if st.max_value else None
+        return lo, hi, int(st.null_count)
+
     def host_job(self, rg, col):
         """A chunk job whose data pointer is HOST memory (for the CPU oracle)."""
         m = self.chunk_meta(rg, col)
@@ -239,6 +248,7 @@ class GpuDecoder:
         _check(self.L.pqg_ctx_create(device, C.byref(h)), "pqg_ctx_create")
         self.ctx = h
         self._bufs = []
+        self.downloaded_bytes = 0  # D2H bytes so far (d2h)
 
     def close(self):
         for p in self._bufs:
@@ -291,6 +301,7 @@ class GpuDecoder:
         out = np.empty(max(nbytes, 0), dtype=np.uint8)
         if nbytes > 0:
             _check(self.L.pqg_memcpy_d2h(self.ctx, out.ctypes.data, C.c_void_p(ptr), nbytes), "pqg_memcpy_d2h")
+            self.downloaded_bytes += nbytes
         return out.view(dtype) if dtype != np.uint8 else out
 
     # ---- decode
@@ -451,6 +462,72 @@ class GpuDecoder:
     def last_assemble_ms(self):
         ms = C.c_float()
         _check(self.L.pqg_last_assemble_ms(self.ctx, C.byref(ms)), "pqg_last_assemble_ms")
+        return ms.value
+
+    # ---- K9s: row predicates and row selection
+    def alloc(self, nbytes):
+        """A device buffer of nbytes (at least 1), freed by free() or close()."""
+        p = C.c_void_p()
+        _check(self.L.pqg_device_alloc(self.ctx, max(nbytes, 1), C.byref(p)), "pqg_device_alloc")
+        self._bufs.append(p)
+        return p.value
+
+    def filter(self, bitmap_ptr, desc, op, literal=None, *, def_ptr=None, values_ptr=None, offsets_ptr=None,
+               num_rows=0, num_values=0, values_bytes=0, combine=abi.COMBINE_SET, dictionary=None):
+        """pqg_filter: `column op literal` into the row bitmap at bitmap_ptr (4 * ceil(num_rows / 32)
+        device bytes; combine: abi.COMBINE_*).  desc: the column's abi.ColumnDesc; literal: bytes in
+        its physical layout; dictionary: the abi.Dictionary (device pointers) of a column whose
+        values are its int32 keys.  Returns the FilterArgs (num_selected, num_valid)."""
+        a = abi.FilterArgs()
+        a.def_levels, a.values, a.offsets = def_ptr or None, values_ptr or None, offsets_ptr or None
+        a.num_rows, a.num_values, a.values_bytes = num_rows, num_values, values_bytes
+        a.col, a.op, a.combine = desc, op, combine
+        lit = np.frombuffer(bytes(literal), dtype=np.uint8) if literal is not None else np.zeros(0, np.uint8)
+        a.literal = lit.ctypes.data if len(lit) else None
+        a.literal_len = len(lit)
+        if dictionary is not None:
+            a.dictionary = C.pointer(dictionary)
+        a.bitmap = bitmap_ptr or None
+        _check(self.L.pqg_filter(self.ctx, C.byref(a)), "pqg_filter")
+        return a
+
+    def filter_result(self, bitmap_ptr, r, desc, op, literal=None, combine=abi.COMBINE_SET, dictionary=None):
+        """filter() on a decoded chunk (a ChunkResult of this decoder's last decode)."""
+        return self.filter(bitmap_ptr, desc, op, literal, def_ptr=r.def_levels, values_ptr=r.values,
+                           offsets_ptr=r.offsets, num_rows=r.num_slots, num_values=r.num_values,
+                           values_bytes=r.values_bytes, combine=combine, dictionary=dictionary)
+
+    def select(self, bitmap_ptr, def_ptr, values_ptr, offsets_ptr, num_rows, num_values, values_bytes, max_def,
+               value_width, count_only=False):
+        """pqg_select: the column compacted by the row bitmap, into newly allocated device buffers
+        of the inputs' sizes (which the outputs never exceed): the SelectArgs, whose out_* are the
+        device pointers (free_select) and rows_out / values_out / bytes_out the counts.  count_only:
+        no buffers, only the counts."""
+        a = abi.SelectArgs()
+        a.bitmap, a.def_levels, a.values, a.offsets = bitmap_ptr or None, def_ptr or None, values_ptr or None, \
+            offsets_ptr or None
+        a.num_rows, a.num_values, a.values_bytes = num_rows, num_values, values_bytes
+        a.max_def, a.value_width = max_def, value_width
+        if not count_only and num_rows > 0:
+            a.out_def_levels = self.alloc(num_rows) if def_ptr and max_def > 0 else None
+            a.out_values = self.alloc(values_bytes)
+            a.out_offsets = self.alloc((num_values + 1) * 8) if value_width == 0 else None
+        try:
+            _check(self.L.pqg_select(self.ctx, C.byref(a)), "pqg_select")
+        except PqgError:
+            self.free_select(a)
+            raise
+        return a
+
+    def free_select(self, a):
+        """Free the outputs select allocated."""
+        for p in (a.out_def_levels, a.out_values, a.out_offsets):
+            if p:
+                self.free(p)
+
+    def last_filter_ms(self):
+        ms = C.c_float()
+        _check(self.L.pqg_last_filter_ms(self.ctx, C.byref(ms)), "pqg_last_filter_ms")
         return ms.value
 
     def download_nested(self, a, chars=None, physical_type=None, flags=0, dictionary=None):
@@ -624,9 +701,11 @@ class FileReader:
         if verify_crc:
             self.dec.set_verify_crc(True)
         self.selected = self._select(columns)
-        self.keep_dict = frozenset(
+        # every column read_dictionary names: a predicate column need not be selected
+        self._dict_named = frozenset(
             i for i in (self._select(tuple(read_dictionary)) if read_dictionary else [])
-            if i in self.selected and self.file.columns[i].desc.physical_type != abi.BOOLEAN)
+            if self.file.columns[i].desc.physical_type != abi.BOOLEAN)
+        self.keep_dict = frozenset(i for i in self._dict_named if i in self.selected)
         self.row_group_position = 0
         self.uploaded_bytes = 0   # H2D bytes so far (projection pushdown check)
         self._rows = None         # NextRow state (pqgpu.rows.RowReader)
@@ -676,8 +755,11 @@ class FileReader:
             self.dec.free(dev)
         return [(rg, c, r) for (rg, c), r in zip(specs, res)]
 
-    def read_row_group(self, rg):
-        """One row group's selected columns, downloaded: {path: DecodedColumn}."""
+    def read_row_group(self, rg, filters=None):
+        """One row group's selected columns, downloaded: {path: DecodedColumn}.  `filters`
+        (pyarrow's DNF, pqgpu.filters) keeps only the rows that pass: see _read_filtered."""
+        if filters is not None:
+            return self._read_filtered(rg, filters)
         self._release()
         specs = [(rg, c) for c in self.selected]
         if not specs:
@@ -689,6 +771,131 @@ class FileReader:
                     for i, ((_, c), r) in enumerate(zip(specs, res))}
         finally:
             self.dec.free(dev)
+
+    def _read_filtered(self, rg, filters):
+        """read_row_group with filters: a list of (column, op, value) tuples (AND) or a list of
+        such lists (OR of ANDs); op is one of == = != < <= > >= in not in, or "is" / "is not" with
+        None.  The predicate columns (selected or not) are decoded in the same batch as the
+        selected ones, pqg_filter builds the row bitmap on the GPU, pqg_select compacts every
+        selected column by it and only the selected rows are downloaded: each DecodedColumn holds
+        them in the layout of an unfiltered read (num_slots == 0 when no row passes).  Columns
+        named in read_dictionary are filtered through their dictionary and come back as keys; a
+        chunk that fell back is filtered materialised.  A repeated column, selected or in a
+        predicate, raises PqgError(UNSUPPORTED) before any GPU work; a chunk that does not decode
+        raises its status, a value that does not fit its column's type ValueError.  No row group
+        is pruned here (prune_row_groups)."""
+        from . import filters as F
+        dnf = F.parse(filters)
+        pred_cols = [self.file.column_index(name) for name in F.columns_of(dnf)]
+        cols = list(self.selected) + [c for c in pred_cols if c not in self.selected]
+        for c in cols:
+            if self.file.columns[c].desc.max_rep > 0:
+                raise PqgError(abi.STATUS_CODES["UNSUPPORTED"], "filtered read of the repeated column %s"
+                               % self.file.columns[c].path.decode())
+        self._release()
+        specs = [(rg, c) for c in cols]
+        res, dev, nbytes = decode_spans(self.file, specs, self.dec, self._dict_named)
+        self.uploaded_bytes += nbytes
+        job = {c: i for i, c in enumerate(cols)}
+        temps = []
+        try:
+            for (_, c), r in zip(specs, res):
+                if r.status != 0:
+                    raise PqgError(r.status, "column %s of row group %d" % (self.file.columns[c].path.decode(), rg))
+            rows = res[0].num_slots
+            if any(r.num_slots != rows for r in res):
+                raise PqgError(abi.STATUS_CODES["INVALID_ARG"], "row group %d: columns of different lengths" % rg)
+            bm_bytes = (rows + 31) // 32 * 4
+            dicts = {}
+
+            def run(term, bitmap, first_combine):
+                c = self.file.column_index(term.column)
+                r, desc = res[job[c]], self.file.columns[c].desc
+                if r.col_flags & abi.COL_KEEP_DICT and c not in dicts:
+                    d = abi.Dictionary()
+                    _check(self.dec.L.pqg_get_dictionary(self.dec.ctx, job[c], C.byref(d)), "pqg_get_dictionary")
+                    dicts[c] = d
+                for k, (op, val, comb) in enumerate(term.steps()):
+                    lit = F.literal(desc, val) if val is not None else None
+                    self.dec.filter_result(bitmap, r, desc, op, lit, first_combine if k == 0 else comb, dicts.get(c))
+
+            def conj_bitmap(terms):
+                """One conjunction into a new device bitmap: the terms chain with AND; an `in`
+                that cannot go first gets a bitmap of its own, AND-ed on the host."""
+                terms = sorted(terms, key=lambda t: t.chains_with_and())  # an `in` first, if any
+                bm = self.dec.alloc(bm_bytes)
+                temps.append(bm)
+                run(terms[0], bm, abi.COMBINE_SET)
+                extra = []
+                for t in terms[1:]:
+                    if t.chains_with_and():
+                        run(t, bm, abi.COMBINE_AND)
+                    else:
+                        e = self.dec.alloc(bm_bytes)
+                        temps.append(e)
+                        run(t, e, abi.COMBINE_SET)
+                        extra.append(e)
+                return bm, extra
+
+            parts = [conj_bitmap(terms) for terms in dnf]
+            bitmap = parts[0][0]
+            if rows > 0 and (len(parts) > 1 or parts[0][1]):
+                # bitmaps of one bit per row, combined on the host: OR of (AND of a conjunction's)
+                acc = np.zeros(bm_bytes, np.uint8)
+                for bm, extra in parts:
+                    w = self.dec.d2h(bm, bm_bytes)
+                    for e in extra:
+                        w = w & self.dec.d2h(e, bm_bytes)
+                    acc |= w
+                _check(self.dec.L.pqg_memcpy_h2d(self.dec.ctx, C.c_void_p(bitmap), acc.ctypes.data, bm_bytes),
+                       "pqg_memcpy_h2d")
+            out = {}
+            for c in self.selected:
+                i, r = job[c], res[job[c]]
+                desc = self.file.columns[c].desc
+                a = self.dec.select(bitmap, r.def_levels, r.values, r.offsets, rows, r.num_values, r.values_bytes,
+                                    desc.max_def, r.value_width)
+                try:
+                    lv = self.dec.d2h(a.out_def_levels, a.rows_out) if desc.max_def > 0 else None
+                    vals = self.dec.d2h(a.out_values, a.bytes_out)
+                    offs = None
+                    if r.value_width == 0:
+                        offs = self.dec.d2h(a.out_offsets, (a.values_out + 1) * 8, np.int64) if a.out_offsets \
+                            else np.zeros(1, np.int64)
+                finally:
+                    self.dec.free_select(a)
+                keep = bool(r.col_flags & abi.COL_KEEP_DICT)
+                out[self.file.columns[c].path.decode()] = DecodedColumn(
+                    r.status, r.error_page, int(a.rows_out), int(a.values_out), r.value_width, lv, None, vals,
+                    self.dec.pages(i), offs, dictionary=self.dec.dictionary(i) if keep else None)
+            return out
+        finally:
+            for p in temps:
+                self.dec.free(p)
+            self.dec.free(dev)
+
+    def prune_row_groups(self, filters):
+        """The row groups whose footer statistics cannot rule out `filters` (as read_row_group
+        takes them), in file order: a row group is dropped when every conjunction holds a term
+        that no row of it can pass.  Conservative: a missing, truncated or odd statistic keeps the
+        row group; FLOAT / DOUBLE never prune on != / not in or on a NaN bound.  Host only."""
+        from . import filters as F
+        dnf = F.parse(filters)
+        keep = []
+        for rg in range(self.file.num_row_groups):
+            rows = self.file.row_group_rows(rg)
+
+            def out(term):
+                c = self.file.column_index(term.column)
+                try:
+                    st = self.file.chunk_stats(rg, c)
+                except PqgError:
+                    return False
+                return F.term_rules_out(self.file.columns[c].desc, term, st, rows)
+
+            if not all(any(out(t) for t in terms) for terms in dnf):
+                keep.append(rg)
+        return keep
 
     def read_row_group_nested(self, rg):
         """One row group's selected columns in Arrow layout: {path:
