@@ -26,6 +26,7 @@
 
 #include "pqgpu.h"
 #include "pqg_common.h"
+#include "pqg_kernels.h"
 #include "pqg_device.h"
 
 namespace pqg {
@@ -685,7 +686,7 @@ int pack_levels_launch(hipStream_t s, const uint8_t* levels, int64_t n, int bw, 
   return hipGetLastError() == hipSuccess ? PQG_OK : PQG_ERR_HIP;
 }
 
-// Host launcher (called from pqg_assemble in pqg_runtime.hip).  seg_scratch
+// Host launcher (called from pqg_assemble in pqg_ops.hip).  seg_scratch
 // holds 2 × nseg int64; tot 2 int64 (device).
 int assemble_launch(hipStream_t s, const pqg_assemble_args* a, int64_t* seg_scratch, int64_t* tot) {
   const int64_t n = a->num_slots;

@@ -15,6 +15,7 @@
 
 #include "pqg_bss.h"
 #include "pqg_common.h"
+#include "pqg_kernels.h"
 #include "pqg_device.h"
 
 namespace pqg {

@@ -268,7 +268,9 @@ constexpr int kPart = 4096;
 constexpr int kLongLev = 32768;
 constexpr int kLevPiece = 16384;
 constexpr int kLongWalk = 16384;
-// counters (ints after the counters base, zeroed by k_page_list)
+// counters (ints after the counters base, zeroed by k_page_list); ctr[0] is the page-list total
+constexpr int kCtrZeroed = 8;     // first of the 16 ints k_page_list zeroes (its `queues` argument)
+constexpr int kCtrSnapSplit = 32; // K2 split: sub-block and segment totals (2 ints, k_snap_plan)
 constexpr int kCtrItems = 48;     // values-stage parts of the batch
 constexpr int kCtrLongLev = 49;   // long level runs
 constexpr int kCtrLevPieces = 50; // pieces of the long level runs
@@ -330,12 +332,26 @@ constexpr int kPwThreads = PQG_PW_THREADS;  // k_str_plain block size (PLAIN byt
 constexpr int kQShards = 8;
 constexpr int kQStride = 32;
 constexpr int kQueueInts = kQShards * kQStride;
-// ints after the counters base (ctr[0] = page-list total): one flag per values
-// stage (PageDev.vmode 0..3 and kModeBss), set by k_page_levels when a page of that stage
-// exists, so an empty stage's kernel exits at once instead of walking the list
-constexpr int kModePresentOff = 1024 + 9 * kQueueInts;
-// BYTE_STREAM_SPLIT pages (k_bss, pqg_bss.hip): their values stage and its flag (4 is the
-// DELTA_*_BYTE_ARRAY flag, 8 kPresentBigDict)
+// The counters buffer: kQueueBase counter ints (the kCtr* slots above), then kQueueSlots regions of
+// kQueueInts ints, one per queue below; region k starts at ctr + kQueueBase + k * kQueueInts.
+constexpr int kQueueBase = 1024;
+constexpr int kQueueSnapSplit = 0;  // sub-blocks of the split snappy decode (k_snap_decode)
+constexpr int kQueueLevels = 1;     // data pages (k_page_levels_w1, or k_page_levels when it runs alone)
+constexpr int kQueueValues = 2;     // parts of the other fixed-width pages (k_values<0>)
+constexpr int kQueueDict4 = 3;      // parts of 4-byte dictionary pages (k_dict4, or k_values<1>)
+constexpr int kQueueStrCount = 4;   // parts of dictionary byte-array pages (k_str_count)
+constexpr int kQueueStrPlain = 5;   // PLAIN byte-array pages (k_str_plain)
+constexpr int kQueueStrCopy = 6;    // parts whose chars are copied (k_str_copy)
+constexpr int kQueueCands = 7;      // the candidate list heads of k_page_cands
+constexpr int kQueueDbp = 8;        // parts of DELTA_BINARY_PACKED pages (k_values<3>)
+// region 9 holds no queue but one flag per values stage (PageDev.vmode 0..3, kModeBss, kModeIdx, and
+// the kPresent* flags), set by k_page_levels when a page of that stage exists, so an empty stage's
+// kernel exits at once instead of walking the list
+constexpr int kQueueFlags = 9;
+constexpr int kModePresentOff = kQueueBase + kQueueFlags * kQueueInts;
+constexpr int kModeDict4 = 1;         // 4-byte dictionary pages (k_dict_plan, k_dict4): their values stage and its flag
+constexpr int kPresentDeltaStr = 4;   // stage flag: a DELTA_LENGTH_BYTE_ARRAY / DELTA_BYTE_ARRAY page (k_str_delta, k_str_dba)
+// BYTE_STREAM_SPLIT pages (k_bss, pqg_bss.hip): their values stage and its flag
 constexpr int kModeBss = 5;
 // RLE_DICTIONARY pages of keep-dictionary jobs (k_dict_idx, pqg_dictidx.hip): their values stage and its flag
 constexpr int kModeIdx = 6;
@@ -357,7 +373,7 @@ constexpr int kQueueBss = 20;   // parts of BYTE_STREAM_SPLIT pages (k_bss)
 constexpr int kQueueCrc = 21;
 constexpr int kCrcTileCtr = 1;
 constexpr int kQueueDictIdx = 22;  // parts of the pages whose keys are kept (k_dict_idx)
-// queue regions zeroed per launch: 0-8, the stage flags (9), 10-22
+// regions zeroed per launch: queues 0-8, the stage flags (kQueueFlags), queues 10-22
 constexpr int kQueueSlots = 23;
 constexpr int kPresentBigDict = 8;  // stage flag (kModePresentOff + 8): a page for k_dict4_big
 

@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 
 #include "pqg_common.h"
+#include "pqg_kernels.h"
 #include "pqg_crc.h"
 #include "pqg_device.h"
 #include "pqg_thrift.h"
@@ -51,8 +52,8 @@ struct GlobalLd {
   }
 };
 
-// the tables, built by the whole workgroup for all of its waves; every thread of the block calls it
-constexpr int kCrcWaves = 4;
+// the tables, built by the whole workgroup for all of its kCrcWaves waves (pqg_kernels.h); every thread of the
+// block calls it
 __device__ __forceinline__ void build_tables_block(const LdsTab& tb) {
   for (int r = 0; r < crc::kTabs; r++) {
     crc::build_round(tb, (int)threadIdx.x, r, 64 * kCrcWaves);

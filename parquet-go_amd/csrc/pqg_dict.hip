@@ -40,6 +40,7 @@
 #include <type_traits>
 
 #include "pqg_common.h"
+#include "pqg_kernels.h"
 #include "pqg_device.h"
 #include "pqg_hybrid.h"
 
@@ -132,8 +133,7 @@ struct PieceShared {
 // LDS of a dictionary workgroup.  kMode 0: run-table pages with a dictionary
 // of <= kDictLdsEntries entries, or none (k_dict4); 3: run-table pages with a
 // larger dictionary, its first kBigLdsEntries entries in LDS (k_dict4_big, one
-// 8-wave workgroup per CU).
-constexpr int kBigWaves = 8;
+// workgroup of kBigWaves waves per CU, pqg_kernels.h).
 constexpr int kBigLdsEntries = 26624;  // 104 KiB: with 8 waves' page stages, one workgroup per CU
 template <int kMode>
 constexpr int dict_waves() { return kMode == 3 ? kBigWaves : kDWaves; }
@@ -593,7 +593,7 @@ __device__ __forceinline__ bool big_dict(const VRec& r) {
 __global__ void __launch_bounds__(256) k_dict_plan(JobDev* jobs, PageDev* pages, const PartRec* parts, const int* total,
                                                    uint8_t* value_arena, const HStream* streams, const RunEnt* runs,
                                                    const BlockDesc* blks, VRec* recs) {
-  if (total[kModePresentOff + 1] == 0) return;
+  if (total[kModePresentOff + kModeDict4] == 0) return;
   const int nt = min(total[kCtrItems], total[kCtrPartsCap]);
   for (int t = blockIdx.x * 256 + threadIdx.x; t < nt; t += gridDim.x * 256) {
     VRec r;
@@ -662,7 +662,7 @@ __device__ __forceinline__ void dict_items(PageDev* pages, const int* total, int
   __shared__ __attribute__((aligned(16))) DictShared<kMode> sh;
   constexpr int kDWaves = dict_waves<kMode>();  // this kernel's waves per workgroup (= pages per item)
   const int lane = lane_id(), wid = (int)(threadIdx.x >> 6);
-  if (total[kModePresentOff + 1] == 0) return;  // no page of this stage
+  if (total[kModePresentOff + kModeDict4] == 0) return;  // no page of this stage
   if (kMode == 3 && total[kModePresentOff + kPresentBigDict] == 0) return;
   if (threadIdx.x == 0) sh.dict_job = -1;
   const int nt = min(total[kCtrItems], total[kCtrPartsCap]);  // work items: pages' parts (k_part_plan)

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 
 #include "pqg_common.h"
+#include "pqg_kernels.h"
 #include "pqg_device.h"
 #include "pqg_hybrid.h"
 
@@ -123,14 +124,13 @@ __global__ void __launch_bounds__(64) k_dict_idx(JobDev* jobs, PageDev* pages, c
 }
 
 // ---- byte-array dictionaries to Arrow layout --------------------------------------------
-// grid (jobs, kExportGridY of pqg_runtime.hip), kExportWaves waves per block; a wave takes runs of 64 entries
+// grid (jobs, kExportGridY), kExportWaves waves per block (pqg_kernels.h); a wave takes runs of 64 entries
 // (one per lane).  Entries of kExportLong bytes or more are copied by the whole wave, one
 // after another (wave_copy: aligned 16-byte destination granules out of funnel-shifted
 // source granules); the shorter ones by their own lane, as dwords where the destination is
 // aligned.  The export publishes dict_chars / dict_aoffs; every source byte lies inside the
 // dictionary page (k_str_dict validated each record), every destination byte below
 // dict_offs[count] - 4 count <= dict_len <= dchars_cap (k_dict_resolve's check).
-constexpr int kExportWaves = 4;
 constexpr int kExportLong = 64;
 
 __global__ void __launch_bounds__(64 * kExportWaves) k_dict_export(JobDev* jobs, const PageDev* pages,

@@ -18,6 +18,7 @@
 
 #include "pqgpu.h"
 #include "pqg_common.h"
+#include "pqg_kernels.h"
 #include "pqg_device.h"
 #include "pqg_filter.h"
 #include "pqg_wavecopy.h"
@@ -237,7 +238,7 @@ __global__ void __launch_bounds__(256) k_sel_write(Sel a, int64_t nseg, const in
   }
 }
 
-// ---- host launchers (called from pqg_filter / pqg_select in pqg_runtime.hip) ------------------------
+// ---- host launchers (called from pqg_filter / pqg_select in pqg_ops.hip) ------------------------
 
 // seg: nseg int64 (+ tot: [0] non-null rows by the scan, [1] selected rows, zeroed here).  dict:
 // the dictionary's device arrays, or null; ebits: 4 * ceil(count / 32) bytes of ctx scratch.

@@ -796,7 +796,7 @@ __device__ __forceinline__ PageStreams page_setup(const JobDev& job, const PageD
     int* present = const_cast<int*>(total) + kModePresentOff;
     if (present[vm] == 0) present[vm] = 1;
     // flag 4: DELTA_LENGTH_BYTE_ARRAY / DELTA_BYTE_ARRAY pages (k_str_delta, k_str_dba)
-    if (vm == 2 && (pg.encoding == 6 || pg.encoding == 7) && present[4] == 0) present[4] = 1;
+    if (vm == 2 && (pg.encoding == 6 || pg.encoding == 7) && present[kPresentDeltaStr] == 0) present[kPresentDeltaStr] = 1;
   }
   return r;
 }

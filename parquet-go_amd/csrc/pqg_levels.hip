@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 
 #include "pqg_common.h"
+#include "pqg_kernels.h"
 #include "pqg_device.h"
 #include "pqg_hybrid.h"
 #include "pqg_levdec.h"

@@ -9,7 +9,7 @@
 // each, so a token costs an LDS read and not a dependent trip to HBM; a run of
 // 0xff extension bytes is skipped a window at a time.
 // Two decoders are built on that, both always compiled (the runtime launches
-// k_lz4_batch unless built or told otherwise, pqg_runtime.hip PQG_LZ4_BATCH):
+// k_lz4_batch unless built or told otherwise, pqg_ctx.h PQG_LZ4_BATCH):
 //  * k_lz4 (step A): sequences are decoded one at a time and executed by the
 //    whole wave.  The latest kLz4Ring output bytes are kept in an LDS ring
 //    beside the stored output: a match whose source lies in the ring is copied
@@ -42,6 +42,7 @@
 #include <hip/hip_runtime.h>
 
 #include "pqg_common.h"
+#include "pqg_kernels.h"
 #include "pqg_device.h"
 #include "pqg_lz4.h"
 #include "pqg_wavecopy.h"
@@ -53,7 +54,7 @@ namespace {
 // The two decoders (DESIGN.md K2l has both measured).  Step A, k_lz4: one sequence at a time, the
 // latest output in an LDS ring.  Step B, k_lz4_batch: up to 64 sequences parsed ahead into lanes and
 // executed together, history read from the stored output through L2.  Both are always built;
-// PQG_LZ4_BATCH (pqg_runtime.hip) says which one the runtime launches by default.
+// PQG_LZ4_BATCH (pqg_ctx.h) says which one the runtime launches by default.
 
 constexpr int kLz4Win = 1024;   // the LDS window of compressed bytes: 64 lanes x 16 bytes
 constexpr int kLz4Ring = 4096;  // the LDS ring of the latest output bytes (a power of two)

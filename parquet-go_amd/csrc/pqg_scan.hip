@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "pqg_common.h"
+#include "pqg_kernels.h"
 #include "pqg_device.h"
 #include "pqg_thrift.h"
 
@@ -1123,8 +1124,8 @@ __global__ void __launch_bounds__(1024) k_page_list(JobDev* jobs, PageDev* pages
     if (j == n_jobs - 1 && y == 0) {
       const int all = off + pages_of(j);
       *total = all < list_cap ? all : list_cap;
-      for (int q = 0; q < 16; q++) queues[q] = 0;  // ctr[8..23]
-      for (int q = kCtrItems; q <= kCtrLongWalk; q++) queues[q - 8] = 0;  // the big-page counters
+      for (int q = 0; q < 16; q++) queues[q] = 0;  // ctr[kCtrZeroed ..]
+      for (int q = kCtrItems; q <= kCtrLongWalk; q++) queues[q - kCtrZeroed] = 0;  // the big-page counters
     }
   }
   __syncthreads();

@@ -31,6 +31,7 @@
 #include <hip/hip_runtime.h>
 
 #include "pqg_common.h"
+#include "pqg_kernels.h"
 #include "pqg_device.h"
 #include "pqg_hybrid.h"
 
@@ -902,7 +903,7 @@ __global__ void __launch_bounds__(64) k_str_delta(JobDev* jobs, PageDev* pages, 
                                                   int* queue, int64_t* offs_arena) {
   __shared__ __attribute__((aligned(16))) DeltaStrShared sh;
   const int lane = lane_id();
-  if (total[kModePresentOff + 4] == 0) return;  // no DELTA_*_BYTE_ARRAY page
+  if (total[kModePresentOff + kPresentDeltaStr] == 0) return;  // no DELTA_*_BYTE_ARRAY page
   for (;;) {
     const int t = queue_next(queue);
     if (t >= *total) return;
@@ -1049,7 +1050,7 @@ __global__ void __launch_bounds__(64) k_str_dba(JobDev* jobs, PageDev* pages, co
                                                 int* queue, uint8_t* value_arena, int64_t* offs_arena) {
   __shared__ __attribute__((aligned(16))) DbaShared sh;
   const int lane = lane_id();
-  if (total[kModePresentOff + 4] == 0) return;
+  if (total[kModePresentOff + kPresentDeltaStr] == 0) return;
   for (;;) {
     const int t = queue_next(queue);
     if (t >= *total) return;
