@@ -158,7 +158,9 @@ typedef struct pqg_column_desc {
  * and so is the flag in pqg_decode_page. */
 enum {
   PQG_COL_UNSIGNED = 1,
-  PQG_COL_KEEP_DICT = 2
+  PQG_COL_KEEP_DICT = 2,
+  PQG_COL_SIGNED_BE = 4  /* pqg_filter only: FIXED_LEN_BYTE_ARRAY values are big-endian two's
+                            complement (a DECIMAL) and order as such; never set by pqg_file_column */
 };
 
 /* One column chunk to decode.  `data` points at the chunk's first page
@@ -554,7 +556,10 @@ enum {
  * PQG_COL_UNSIGNED in col.flags; FLOAT / DOUBLE IEEE (NaN, as value or as literal,
  * fails everything but NE, which it passes; -0.0 == 0.0); BOOLEAN one byte, 0 < 1;
  * BYTE_ARRAY and FIXED_LEN_BYTE_ARRAY (type_length >= 1) unsigned lexicographic over
- * the bytes (a proper prefix sorts first, the empty string lowest); INT96, and FLBA with
+ * the bytes (a proper prefix sorts first, the empty string lowest); with PQG_COL_SIGNED_BE in
+ * col.flags a FIXED_LEN_BYTE_ARRAY column orders as big-endian two's complement (a DECIMAL: the
+ * same compare with bit 7 of byte 0 flipped on both sides), and the flag on any other physical
+ * type is PQG_ERR_INVALID_ARG; INT96, and FLBA with
  * type_length < 1, are PQG_ERR_UNSUPPORTED, and so is col.max_rep > 0.  `literal` is
  * HOST memory in the column's physical little-endian layout (ignored by IS_NULL /
  * NOT_NULL): a length other than 4 / 8 / 1 / type_length for a fixed-width type is
@@ -617,6 +622,42 @@ int pqg_select(pqg_ctx* ctx, pqg_select_args* args);
  * pair on the ctx stream; the literal upload and the count read-back excluded). */
 int pqg_last_filter_ms(pqg_ctx* ctx, float* ms);
 
+/* pqg_convert: decoded dense values of a logical type into the layout Arrow gives it.
+ * DECIMAL_BE: big-endian two's complement of in_width bytes (FIXED_LEN_BYTE_ARRAY decimals), or
+ * with `offsets` of each value's own length (BYTE_ARRAY decimals), to out_width (16 / 32)
+ * little-endian bytes, sign-extended: out[i*ow + k] = in[i*w + w-1-k] for k < w, the sign byte
+ * above.  DECIMAL_INT: 4 / 8 little-endian bytes sign-extended to out_width.  INT96_TIME:
+ * (nanos of the day u64, julian day i32) to int64
+ *   (int64)(day - 2440588) * units_per_day + (int64)(nanos / ns_per_unit)
+ * with an unsigned, truncating divide and a multiply and add that wrap in 64 bits (a nil entry's
+ * zero bytes convert like any value).  `values` may have any alignment (a dictionary read in
+ * place); `out` is caller-allocated, 16-byte aligned, num_values * out_width bytes, and must not
+ * overlap the input.  PQG_ERR_INVALID_ARG: an in_width / out_width / unit the kind does not take,
+ * in_width > out_width, values_bytes < num_values * in_width, a misaligned `out`.  BYTE_ARRAY
+ * decimals are counted first: a value of length 0 or above out_width (Arrow's FromBigEndian
+ * rejects both), or whose offsets are negative, not ascending or past values_bytes, is a bad
+ * value; with any, num_bad is set and the call is PQG_ERR_SIZE.  The call enqueues on the ctx
+ * stream and waits; it does nothing for num_values == 0; a failing call writes no output. */
+enum {
+  PQG_CONV_DECIMAL_BE = 0,
+  PQG_CONV_DECIMAL_INT = 1,
+  PQG_CONV_INT96_TIME = 2
+};
+enum { PQG_UNIT_NONE = 0, PQG_UNIT_SECONDS, PQG_UNIT_MILLIS, PQG_UNIT_MICROS, PQG_UNIT_NANOS };
+typedef struct pqg_convert_args {
+  const uint8_t* values;   /* DEVICE: dense values or chars; any alignment                      */
+  const int64_t* offsets;  /* DEVICE: BYTE_ARRAY decimals (num_values + 1), else NULL            */
+  int64_t num_values, values_bytes;
+  int32_t kind, in_width;  /* in_width: DECIMAL_BE 1..32 (0 with offsets), DECIMAL_INT 4 / 8, INT96 12 */
+  int32_t out_width;       /* decimals: 16 or 32; INT96_TIME: 8                                  */
+  int32_t unit;            /* INT96_TIME: PQG_UNIT_SECONDS .. PQG_UNIT_NANOS                     */
+  uint8_t* out;            /* DEVICE, 16-byte aligned, num_values * out_width bytes              */
+  int64_t num_bad;         /* out: bad BYTE_ARRAY decimals                                       */
+} pqg_convert_args;
+int pqg_convert(pqg_ctx* ctx, pqg_convert_args* args);
+/* Device time (ms) of the kernels of the last pqg_convert call (the count pass included). */
+int pqg_last_convert_ms(pqg_ctx* ctx, float* ms);
+
 /* ---- host-side planner: footer / schema (file_meta.go:14-62, schema.go) --- */
 typedef struct pqg_file pqg_file;
 
@@ -667,6 +708,19 @@ typedef struct pqg_chunk_stats {
   int64_t null_count;                    /* -1 = absent */
 } pqg_chunk_stats;
 int pqg_file_chunk_stats(const pqg_file* f, int row_group, int col, pqg_chunk_stats* out);
+
+/* The logical type of a leaf: SchemaElement.logicalType (field 10) when the element has one
+ * that parses, else what converted_type (6) with scale (7) / precision (8) says (UTF8 STRING,
+ * DECIMAL, DATE, TIME_MILLIS / TIME_MICROS TIME, TIMESTAMP_MILLIS / TIMESTAMP_MICROS TIMESTAMP
+ * (utc = 1, as the format defines them), UINT_* / INT_* INTEGER, ENUM, JSON, BSON).  Nothing
+ * is validated: a precision of 0 is reported as 0.  Fields that do not apply are 0. */
+enum { PQG_LT_NONE = 0, PQG_LT_STRING, PQG_LT_ENUM, PQG_LT_DECIMAL, PQG_LT_DATE, PQG_LT_TIME,
+       PQG_LT_TIMESTAMP, PQG_LT_INTEGER, PQG_LT_JSON, PQG_LT_BSON, PQG_LT_UUID, PQG_LT_FLOAT16, PQG_LT_OTHER };
+typedef struct pqg_logical_type {
+  int32_t kind, precision, scale, unit, utc, bit_width, is_signed;
+  int32_t converted_type;   /* SchemaElement.converted_type as stored, -1 when absent */
+} pqg_logical_type;
+int pqg_file_column_logical(const pqg_file* f, int col, pqg_logical_type* out);
 
 /* The schema tree below the root, depth first (makeSchema / readGroupSchema
  * schema.go:789-894, 996-1025): what NextRow's row assembly walks

@@ -126,6 +126,8 @@ struct pqg_ctx {
   DevBuf flt_buf;  // K9s: per-segment counts + totals, the literal's bytes, the dictionary-entry bitmap
   float flt_ms = 0.f;    // device time of the last pqg_filter / pqg_select
   bool flt_lds = true;   // entry bitmaps of up to flt::kLdsEntries entries are staged in LDS (PQG_FILTER_LDS=0: read through L2)
+  DevBuf conv_buf;       // K10: the count of bad BYTE_ARRAY decimals
+  float conv_ms = 0.f;   // device time of the last pqg_convert
   DevBuf offs_arena, doffs_arena;  // K7: value offsets (int64), dictionary record starts
   DevBuf aoffs_arena, dchars_arena;  // K4i: byte-array dictionaries in Arrow layout (k_dict_export): offsets (laid out as
                                      // doffs_arena), chars
@@ -155,11 +157,12 @@ struct pqg_ctx {
   int n_jobs = 0;
   int64_t list_cap = 0;
   // every event of the context, created and destroyed as one array; the stages' names are views of it
-  hipEvent_t events[pqg::kStages + 1 + 4 + 2 + 2];
+  hipEvent_t events[pqg::kStages + 1 + 4 + 2 + 2 + 4];
   hipEvent_t* const ev = events;                    // [kStages + 1]: the pipeline's stage boundaries
   hipEvent_t* const ev_k8 = ev + pqg::kStages + 1;  // K8: [0,1] assemble / list count, [2,3] list write
   hipEvent_t* const ev_crc = ev_k8 + 4;             // K1c: [0,1] around the checksum kernels
   hipEvent_t* const ev_flt = ev_crc + 2;            // K9s: [0,1] around pqg_filter / pqg_select
+  hipEvent_t* const ev_conv = ev_flt + 2;           // K10: [0,1] pqg_convert's count pass, [2,3] its write pass
   float k8_ms = 0.f;     // device time of the last pqg_assemble / pqg_assemble_list
   bool timed = true;
   bool last_timed = false;              // the last pipeline launch recorded the stage events

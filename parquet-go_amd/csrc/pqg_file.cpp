@@ -29,7 +29,11 @@ struct Elem {
   bool has_type = false, has_tl = false, has_rep = false, has_nc = false, has_ct = false;
   int32_t type = 0, type_length = 0, rep = 0, num_children = 0, converted = 0;
   bool unsigned_int = false;
+  bool has_scale = false, has_precision = false;
+  int32_t scale = 0, precision = 0;
+  pqg_logical_type lt;  // from the LogicalType union alone; kind PQG_LT_NONE without one that parses
   std::string name;
+  Elem() { memset(&lt, 0, sizeof(lt)); }
 };
 
 struct ChunkM {
@@ -44,6 +48,7 @@ struct ChunkM {
 
 struct Leaf {
   pqg_column_desc desc;
+  pqg_logical_type logical;
   std::string path;
 };
 
@@ -124,6 +129,70 @@ struct Parser {
       return 0;
     });
   }
+  // LogicalType union: the member set last wins, as in a thrift union read
+  static void logical(const uint8_t* p, int64_t n, pqg_logical_type* out) {
+    Parser q(p, n);
+    pqg_logical_type lt;
+    memset(&lt, 0, sizeof(lt));
+    const bool ok = q.fields([&](int t, int id) -> int {
+      if (t != T_STRUCT) return 0;
+      pqg_logical_type m;
+      memset(&m, 0, sizeof(m));
+      int kind = PQG_LT_OTHER;
+      switch (id) {
+        case 1: kind = PQG_LT_STRING; break;
+        case 4: kind = PQG_LT_ENUM; break;
+        case 5: kind = PQG_LT_DECIMAL; break;
+        case 6: kind = PQG_LT_DATE; break;
+        case 7: kind = PQG_LT_TIME; break;
+        case 8: kind = PQG_LT_TIMESTAMP; break;
+        case 10: kind = PQG_LT_INTEGER; break;
+        case 12: kind = PQG_LT_JSON; break;
+        case 13: kind = PQG_LT_BSON; break;
+        case 14: kind = PQG_LT_UUID; break;
+        case 15: kind = PQG_LT_FLOAT16; break;
+      }
+      m.kind = kind;
+      const bool okm = q.fields([&](int t2, int id2) -> int {
+        int32_t v;
+        if (kind == PQG_LT_DECIMAL && t2 == T_I32 && (id2 == 1 || id2 == 2)) {
+          if (q.c.i32(&v)) return -1;
+          (id2 == 1 ? m.scale : m.precision) = v;
+          return 1;
+        }
+        if ((kind == PQG_LT_TIME || kind == PQG_LT_TIMESTAMP) && id2 == 1 && t2 == T_BOOL) {
+          bool b;
+          if (q.c.read_bool(&b)) return -1;
+          m.utc = b ? 1 : 0;
+          return 1;
+        }
+        if ((kind == PQG_LT_TIME || kind == PQG_LT_TIMESTAMP) && id2 == 2 && t2 == T_STRUCT) {
+          // TimeUnit union: 1 MILLIS, 2 MICROS, 3 NANOS (empty structs)
+          return q.fields([&](int t3, int id3) -> int {
+            if (t3 == T_STRUCT && id3 >= 1 && id3 <= 3) m.unit = PQG_UNIT_MILLIS + (id3 - 1);
+            return 0;
+          }) ? 1 : -1;
+        }
+        if (kind == PQG_LT_INTEGER && id2 == 1 && t2 == T_BYTE) {
+          uint8_t b;
+          if (q.c.byte(&b)) return -1;
+          m.bit_width = (int8_t)b;
+          return 1;
+        }
+        if (kind == PQG_LT_INTEGER && id2 == 2 && t2 == T_BOOL) {
+          bool b;
+          if (q.c.read_bool(&b)) return -1;
+          m.is_signed = b ? 1 : 0;
+          return 1;
+        }
+        return 0;
+      });
+      if (!okm) return -1;
+      lt = m;
+      return 1;
+    });
+    if (ok && q.c.pos == n) *out = lt;
+  }
   bool elem(Elem* e) {
     return fields([&](int t, int id) -> int {
       int32_t v;
@@ -134,7 +203,18 @@ struct Parser {
         case 4: if (t == T_STRING) { return str(&e->name) ? 1 : -1; } break;
         case 5: if (t == T_I32) { if (c.i32(&v)) return -1; e->num_children = v; e->has_nc = true; return 1; } break;
         case 6: if (t == T_I32) { if (c.i32(&v)) return -1; e->converted = v; e->has_ct = true; return 1; } break;
-        case 10: if (t == T_STRUCT) { return logical_unsigned(&e->unsigned_int) ? 1 : -1; } break;
+        case 7: if (t == T_I32) { if (c.i32(&v)) return -1; e->scale = v; e->has_scale = true; return 1; } break;
+        case 8: if (t == T_I32) { if (c.i32(&v)) return -1; e->precision = v; e->has_precision = true; return 1; } break;
+        case 10:
+          if (t == T_STRUCT) {
+            // read as before (its parse decides whether the footer opens), then once more from its
+            // own bytes for the logical type: what that finds or fails on changes nothing else
+            const int64_t s0 = c.pos;
+            if (!logical_unsigned(&e->unsigned_int)) return -1;
+            logical(c.src.p + s0, c.pos - s0, &e->lt);
+            return 1;
+          }
+          break;
       }
       return 0;
     });
@@ -263,6 +343,39 @@ bool read_schema(const std::vector<Elem>& s, size_t& idx, const std::string& nam
                    (e.type == 2 && e.converted == 14)))
     uns = true;
   l.desc.flags = uns ? 1 : 0;
+  l.logical = e.lt;
+  if (l.logical.kind == PQG_LT_NONE && e.has_ct) {  // a writer of converted types only
+    pqg_logical_type& g = l.logical;
+    const int ct = e.converted;
+    switch (ct) {
+      case 0: g.kind = PQG_LT_STRING; break;
+      case 4: g.kind = PQG_LT_ENUM; break;
+      case 5:
+        g.kind = PQG_LT_DECIMAL;
+        g.scale = e.has_scale ? e.scale : 0;
+        g.precision = e.has_precision ? e.precision : 0;
+        break;
+      case 6: g.kind = PQG_LT_DATE; break;
+      case 7: case 8:
+        g.kind = PQG_LT_TIME;
+        g.unit = ct == 7 ? PQG_UNIT_MILLIS : PQG_UNIT_MICROS;
+        g.utc = 1;
+        break;
+      case 9: case 10:
+        g.kind = PQG_LT_TIMESTAMP;
+        g.unit = ct == 9 ? PQG_UNIT_MILLIS : PQG_UNIT_MICROS;
+        g.utc = 1;
+        break;
+      case 11: case 12: case 13: case 14: case 15: case 16: case 17: case 18:
+        g.kind = PQG_LT_INTEGER;
+        g.bit_width = 8 << ((ct - 11) & 3);
+        g.is_signed = ct >= 15;
+        break;
+      case 19: g.kind = PQG_LT_JSON; break;
+      case 20: g.kind = PQG_LT_BSON; break;
+    }
+  }
+  l.logical.converted_type = e.has_ct ? e.converted : -1;
   l.path = name.empty() ? e.name : name + "." + e.name;
   nodes.push_back(SNode{e.name, e.rep, 0, (int32_t)out.size(), d, r});
   out.push_back(l);
@@ -396,6 +509,12 @@ int pqg_file_column(const pqg_file* f, int col, pqg_column_info* out) {
   if (f->leaves[(size_t)col].path.size() >= sizeof(out->path)) return PQG_ERR_METADATA;  // no truncated paths
   out->desc = f->leaves[(size_t)col].desc;
   strncpy(out->path, f->leaves[(size_t)col].path.c_str(), sizeof(out->path) - 1);
+  return PQG_OK;
+}
+
+int pqg_file_column_logical(const pqg_file* f, int col, pqg_logical_type* out) {
+  if (!f || !out || col < 0 || col >= (int)f->leaves.size()) return PQG_ERR_INVALID_ARG;
+  *out = f->leaves[(size_t)col].logical;
   return PQG_OK;
 }
 

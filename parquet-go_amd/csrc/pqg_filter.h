@@ -10,7 +10,8 @@
 // belongs to the r-th non-null row.  Comparison orders (include/pqgpu.h, pqg_filter):
 // signed / unsigned integers, IEEE floats (a NaN on either side is unordered: it fails every
 // operator but NE), BOOLEAN as a byte, byte strings unsigned lexicographic (a proper prefix
-// sorts first).  A null row passes IS_NULL only.
+// sorts first); K_FLBA_SBE (PQG_COL_SIGNED_BE: a DECIMAL's big-endian two's complement) the same
+// with bit 7 of byte 0 flipped on both sides.  A null row passes IS_NULL only.
 //
 // IO: u8 / u32 / u64 (address) loads and st8 / st32 / st64 (address, value) stores, every
 // access naturally aligned; eword(base, j) reads dword j of the dictionary-entry bitmap (the
@@ -30,12 +31,12 @@ constexpr int kLdsEntries = 65536;  // dictionaries up to this many entries may 
 
 enum : int { OP_EQ = 0, OP_NE = 1, OP_LT = 2, OP_LE = 3, OP_GT = 4, OP_GE = 5, OP_IS_NULL = 6, OP_NOT_NULL = 7 };
 enum : int { M_SET = 0, M_AND = 1, M_OR = 2 };
-enum : int { K_I32 = 0, K_U32, K_I64, K_U64, K_F32, K_F64, K_U8, K_FLBA, K_BYTES };
+enum : int { K_I32 = 0, K_U32, K_I64, K_U64, K_F32, K_F64, K_U8, K_FLBA, K_BYTES, K_FLBA_SBE };
 enum : int { C_LT = -1, C_EQ = 0, C_GT = 1, C_UN = 2 };  // C_UN: unordered (NaN)
 
 // One comparison, as the kernels take it.
 struct Pred {
-  int kind, op, width;  // width: bytes per fixed-width value (K_FLBA: type_length; K_BYTES: 0)
+  int kind, op, width;  // width: bytes per fixed-width value (K_FLBA / K_FLBA_SBE: type_length; K_BYTES: 0)
   uint64_t lit;         // numeric kinds: the literal's bits
   uintptr_t lit_bytes;  // byte kinds: the literal's bytes (an address the IO reads)
   int64_t lit_len;
@@ -93,13 +94,15 @@ __host__ __device__ __forceinline__ int cmp_bits(int kind, uint64_t a, uint64_t 
 }
 
 // bytes [a, a + alen) against [b, b + blen): unsigned lexicographic, a proper prefix first.
-// zero_a: a reads as alen zero bytes (a dictionary's nil entry) and is not loaded.
+// zero_a: a reads as alen zero bytes (a dictionary's nil entry) and is not loaded.  flip0 is
+// xor-ed into byte 0 of both sides: 0x80 orders big-endian two's complement (K_FLBA_SBE).
 template <class IO>
 __host__ __device__ __forceinline__ int cmp_bytes(const IO& io, uintptr_t a, int64_t alen, uintptr_t b, int64_t blen,
-                                                  bool zero_a = false) {
+                                                  bool zero_a = false, uint32_t flip0 = 0) {
   const int64_t n = alen < blen ? alen : blen;
   for (int64_t i = 0; i < n; i++) {
-    const uint32_t x = zero_a ? 0u : io.u8(a + (uintptr_t)i), y = io.u8(b + (uintptr_t)i);
+    const uint32_t f = i == 0 ? flip0 : 0u;
+    const uint32_t x = (zero_a ? 0u : io.u8(a + (uintptr_t)i)) ^ f, y = io.u8(b + (uintptr_t)i) ^ f;
     if (x != y) return x < y ? C_LT : C_GT;
   }
   return alen < blen ? C_LT : alen > blen ? C_GT : C_EQ;
@@ -124,6 +127,8 @@ __host__ __device__ __forceinline__ int cmp_value(const IO& io, const Pred& p, u
     return cmp_bytes(io, values + (uintptr_t)o0, o1 - o0, p.lit_bytes, p.lit_len);
   }
   if (p.kind == K_FLBA) return cmp_bytes(io, values + (uintptr_t)idx * (uintptr_t)p.width, p.width, p.lit_bytes, p.lit_len);
+  if (p.kind == K_FLBA_SBE)
+    return cmp_bytes(io, values + (uintptr_t)idx * (uintptr_t)p.width, p.width, p.lit_bytes, p.lit_len, false, 0x80u);
   return cmp_bits(p.kind, load_bits(io, p.kind, values, idx), p.lit);
 }
 
@@ -136,10 +141,11 @@ __host__ __device__ __forceinline__ bool entry_pass(const IO& io, const Pred& p,
     const int64_t w = p.width;
     if (e == nil_entry || (e + 1) * w > values_bytes) {
       if (p.kind == K_FLBA) return op_pass(p.op, cmp_bytes(io, 0, w, p.lit_bytes, p.lit_len, true));
+      if (p.kind == K_FLBA_SBE) return op_pass(p.op, cmp_bytes(io, 0, w, p.lit_bytes, p.lit_len, true, 0x80u));
       return op_pass(p.op, cmp_bits(p.kind, 0, p.lit));
     }
   }
-  if (p.kind != K_BYTES && p.kind != K_FLBA) {
+  if (p.kind != K_BYTES && p.kind != K_FLBA && p.kind != K_FLBA_SBE) {
     // a dictionary page's entries lie where the file put them: no alignment, so byte loads
     uint64_t bits = 0;
     for (int k = 0; k < p.width; k++) bits |= (uint64_t)io.u8(values + (uintptr_t)(e * p.width + k)) << (8 * k);

@@ -1,7 +1,7 @@
 // pqg_kernels.h — the one declaration of everything launched across translation units.
 //
 // Every __global__ kernel that another file than its own launches, the host *_launch entries of
-// pqg_assemble.hip and pqg_filter.hip, the profile readers, and the launch-shape constants that a
+// pqg_assemble.hip, pqg_filter.hip and pqg_convert.hip, the profile readers, and the launch-shape constants that a
 // kernel and its launch site share.  The launching files (pqg_runtime.hip, pqg_ops.hip) and every
 // file that defines one of these include it, so a declaration that drifts from its definition is
 // an overload nobody defines and the link (-Wl,-z,defs) fails.
@@ -117,7 +117,7 @@ __global__ void k_str_dba(JobDev* jobs, PageDev* pages, const int* list, const i
 __global__ void k_str_copy(JobDev* jobs, PageDev* pages, const PartRec* parts, const int* total, int* queue,
                            uint8_t* value_arena, int64_t* offs_arena);
 
-// ---- host launchers: pqg_assemble.hip (K8) and pqg_filter.hip (K9s)
+// ---- host launchers: pqg_assemble.hip (K8), pqg_filter.hip (K9s) and pqg_convert.hip (K10)
 int assemble_launch(hipStream_t s, const pqg_assemble_args* a, int64_t* seg_scratch, int64_t* tot);
 int list_count_launch(hipStream_t s, const pqg_list_args* a, int64_t* seg_scratch, int64_t* tot);
 int list_write_launch(hipStream_t s, const pqg_list_args* a, int64_t* seg_scratch);
@@ -127,6 +127,8 @@ int pack_levels_launch(hipStream_t s, const uint8_t* levels, int64_t n, int bw, 
 int filter_launch(hipStream_t s, const flt::Pred& p, const flt::Col& c, const pqg_dictionary* dict, uint32_t* ebits,
                   uint8_t* bitmap, int64_t n, int mode, bool lds, int64_t* seg, int64_t* tot);
 int select_launch(hipStream_t s, const flt::Sel& a, int64_t* seg, int64_t* tot);
+int convert_count_launch(hipStream_t s, const pqg_convert_args* a, int64_t* tot);
+int convert_launch(hipStream_t s, const pqg_convert_args* a);
 
 #ifdef PQG_PROFILE
 // read + reset a translation unit's in-kernel phase counters (64 slots each; pqg_debug_counters)

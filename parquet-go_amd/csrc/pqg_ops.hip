@@ -8,6 +8,7 @@
 #include <cstring>
 
 #include "pqg_ctx.h"
+#include "pqg_convert.h"
 #include "pqg_crc.h"
 #include "pqg_filter.h"
 #include "pqg_kernels.h"
@@ -321,6 +322,8 @@ int pqg_filter(pqg_ctx* c, pqg_filter_args* a) {
   if (a->col.max_rep > 0) return PQG_ERR_UNSUPPORTED;
   const int type = a->col.physical_type;
   const bool uns = (a->col.flags & PQG_COL_UNSIGNED) != 0;
+  const bool sbe = (a->col.flags & PQG_COL_SIGNED_BE) != 0;  // FLBA only: big-endian two's complement order
+  if (sbe && type != PQG_FIXED_LEN_BYTE_ARRAY) return PQG_ERR_INVALID_ARG;
   flt::Pred p;
   memset(&p, 0, sizeof(p));
   p.op = a->op;
@@ -333,13 +336,13 @@ int pqg_filter(pqg_ctx* c, pqg_filter_args* a) {
     case PQG_BYTE_ARRAY: p.kind = flt::K_BYTES; p.width = 0; break;
     case PQG_FIXED_LEN_BYTE_ARRAY:
       if (a->col.type_length < 1) return PQG_ERR_UNSUPPORTED;
-      p.kind = flt::K_FLBA;
+      p.kind = sbe ? flt::K_FLBA_SBE : flt::K_FLBA;
       p.width = a->col.type_length;
       break;
     default: return PQG_ERR_UNSUPPORTED;  // INT96
   }
   const bool cmp = a->op != PQG_OP_IS_NULL && a->op != PQG_OP_NOT_NULL;
-  const bool bytes = p.kind == flt::K_BYTES || p.kind == flt::K_FLBA;
+  const bool bytes = p.kind == flt::K_BYTES || p.kind == flt::K_FLBA || p.kind == flt::K_FLBA_SBE;
   if (cmp) {
     if (a->literal_len < 0 || (a->literal_len > 0 && !a->literal)) return PQG_ERR_INVALID_ARG;
     if (p.kind != flt::K_BYTES && a->literal_len != p.width) return PQG_ERR_INVALID_ARG;
@@ -451,6 +454,63 @@ int pqg_select(pqg_ctx* c, pqg_select_args* a) {
 int pqg_last_filter_ms(pqg_ctx* c, float* ms) {
   if (!c || !ms) return PQG_ERR_INVALID_ARG;
   *ms = c->flt_ms;
+  return PQG_OK;
+}
+
+// K10: logical-type conversion of dense values (pqg_convert.hip).
+int pqg_convert(pqg_ctx* c, pqg_convert_args* a) {
+  if (!c || !a || a->num_values < 0 || a->values_bytes < 0) return PQG_ERR_INVALID_ARG;
+  a->num_bad = 0;
+  const int64_t n = a->num_values;
+  const int w = a->in_width, ow = a->out_width;
+  const bool var = a->offsets != nullptr;
+  switch (a->kind) {
+    case PQG_CONV_DECIMAL_BE:
+      if (ow != 16 && ow != 32) return PQG_ERR_INVALID_ARG;
+      if (var ? w != 0 : (w < 1 || w > 32 || w > ow)) return PQG_ERR_INVALID_ARG;
+      break;
+    case PQG_CONV_DECIMAL_INT:
+      if ((ow != 16 && ow != 32) || (w != 4 && w != 8) || var) return PQG_ERR_INVALID_ARG;
+      break;
+    case PQG_CONV_INT96_TIME:
+      if (ow != 8 || w != 12 || var || a->unit < PQG_UNIT_SECONDS || a->unit > PQG_UNIT_NANOS) return PQG_ERR_INVALID_ARG;
+      break;
+    default: return PQG_ERR_INVALID_ARG;
+  }
+  if (!var && a->values_bytes / w < n) return PQG_ERR_INVALID_ARG;  // values_bytes < n * w, without the product
+  if (n > INT64_MAX / ow) return PQG_ERR_INVALID_ARG;
+  if (((uintptr_t)a->out & 15) || (var && ((uintptr_t)a->offsets & 7))) return PQG_ERR_INVALID_ARG;
+  c->conv_ms = 0.f;
+  if (n == 0) return PQG_OK;
+  if (!a->out || (!a->values && a->values_bytes > 0) || (!var && !a->values)) return PQG_ERR_INVALID_ARG;
+  hipSetDevice(c->device);
+  float count_ms = 0.f;
+  if (var) {
+    if (c->conv_buf.grow(sizeof(int64_t))) return PQG_ERR_HIP;
+    int64_t* tot = (int64_t*)c->conv_buf.p;
+    int64_t bad = 0;
+    const int e = count_pass(c, c->ev_conv, [&] { return convert_count_launch(c->stream, a, tot); }, tot, &bad, 1, &count_ms);
+    if (e) return e;
+    c->conv_ms = count_ms;
+    if (bad > 0) {
+      a->num_bad = bad;
+      return PQG_ERR_SIZE;
+    }
+  }
+  hipEventRecord(c->ev_conv[2], c->stream);
+  int e = convert_launch(c->stream, a);
+  if (e) return e;
+  hipEventRecord(c->ev_conv[3], c->stream);
+  e = hip_ok(hipStreamSynchronize(c->stream));
+  float ms = 0.f;
+  hipEventElapsedTime(&ms, c->ev_conv[2], c->ev_conv[3]);
+  c->conv_ms = count_ms + ms;
+  return e;
+}
+
+int pqg_last_convert_ms(pqg_ctx* c, float* ms) {
+  if (!c || !ms) return PQG_ERR_INVALID_ARG;
+  *ms = c->conv_ms;
   return PQG_OK;
 }
 

@@ -66,6 +66,9 @@ def lib():
         "pqg_filter": ([P, C.POINTER(abi.FilterArgs)], I),
         "pqg_select": ([P, C.POINTER(abi.SelectArgs)], I),
         "pqg_last_filter_ms": ([P, C.POINTER(C.c_float)], I),
+        "pqg_convert": ([P, C.POINTER(abi.ConvertArgs)], I),
+        "pqg_last_convert_ms": ([P, C.POINTER(C.c_float)], I),
+        "pqg_file_column_logical": ([P, I, C.POINTER(abi.LogicalType)], I),
     }
     for name, (args, res) in sig.items():
         # a library named by PQG_LIB may be an older build (A/B runs against a parent's library):
@@ -88,4 +91,5 @@ EXPORTED = [
     "pqg_file_num_columns", "pqg_file_num_row_groups", "pqg_file_num_rows", "pqg_file_row_group_rows",
     "pqg_file_column", "pqg_file_chunk", "pqg_file_num_schema_nodes", "pqg_file_schema_node",
     "pqg_get_dictionary", "pqg_file_chunk_stats", "pqg_filter", "pqg_select", "pqg_last_filter_ms",
+    "pqg_convert", "pqg_last_convert_ms", "pqg_file_column_logical",
 ]

@@ -55,6 +55,7 @@ FIXED_WIDTH = {BOOLEAN: 1, INT32: 4, INT64: 8, INT96: 12, FLOAT: 4, DOUBLE: 8}
 
 # pqg_column_desc.flags
 COL_UNSIGNED, COL_KEEP_DICT = 1, 2
+COL_SIGNED_BE = 4  # pqg_filter only: FLBA values order as big-endian two's complement (a DECIMAL)
 
 
 class ColumnDesc(C.Structure):
@@ -241,6 +242,31 @@ class SelectArgs(C.Structure):
                 ("max_def", C.c_int32), ("value_width", C.c_int32),
                 ("out_def_levels", C.c_void_p), ("out_values", C.c_void_p), ("out_offsets", C.c_void_p),
                 ("rows_out", C.c_int64), ("values_out", C.c_int64), ("bytes_out", C.c_int64)]
+
+
+# pqg_logical_type.kind / .unit
+(LT_NONE, LT_STRING, LT_ENUM, LT_DECIMAL, LT_DATE, LT_TIME, LT_TIMESTAMP, LT_INTEGER, LT_JSON, LT_BSON, LT_UUID,
+ LT_FLOAT16, LT_OTHER) = range(13)
+UNIT_NONE, UNIT_SECONDS, UNIT_MILLIS, UNIT_MICROS, UNIT_NANOS = range(5)
+UNITS = {"s": UNIT_SECONDS, "ms": UNIT_MILLIS, "us": UNIT_MICROS, "ns": UNIT_NANOS}
+UNIT_PER_SECOND = {UNIT_SECONDS: 1, UNIT_MILLIS: 10 ** 3, UNIT_MICROS: 10 ** 6, UNIT_NANOS: 10 ** 9}
+
+
+class LogicalType(C.Structure):
+    """pqg_logical_type (include/pqgpu.h): the logical type of a leaf column."""
+    _fields_ = [("kind", C.c_int32), ("precision", C.c_int32), ("scale", C.c_int32), ("unit", C.c_int32),
+                ("utc", C.c_int32), ("bit_width", C.c_int32), ("is_signed", C.c_int32), ("converted_type", C.c_int32)]
+
+
+# pqg_convert kinds
+CONV_DECIMAL_BE, CONV_DECIMAL_INT, CONV_INT96_TIME = range(3)
+
+
+class ConvertArgs(C.Structure):
+    """pqg_convert_args (include/pqgpu.h, K10)."""
+    _fields_ = [("values", C.c_void_p), ("offsets", C.c_void_p), ("num_values", C.c_int64), ("values_bytes", C.c_int64),
+                ("kind", C.c_int32), ("in_width", C.c_int32), ("out_width", C.c_int32), ("unit", C.c_int32),
+                ("out", C.c_void_p), ("num_bad", C.c_int64)]
 
 
 def status_name(code):

@@ -6,6 +6,11 @@ Operators: == = != < <= > >= in not in, and (col, "is", None) / (col, "is not", 
 Comparison orders are pqg_filter's (include/pqgpu.h): signed / unsigned integers, IEEE floats
 (NaN fails everything but !=), BOOLEAN 0 < 1, byte strings unsigned lexicographic.  A null row
 fails every comparison and passes only `is null`.
+
+With a column's abi.LogicalType, literals may be typed (pqgpu.logical): decimal.Decimal / int on a
+DECIMAL column, datetime / np.datetime64 on a TIMESTAMP column, date on a DATE column; and a
+FIXED_LEN_BYTE_ARRAY decimal (abi.COL_SIGNED_BE in the description's flags) orders as the
+big-endian two's complement it is.
 """
 import struct
 
@@ -89,9 +94,25 @@ def columns_of(dnf):
     return seen
 
 
-def literal(desc, value):
+def signed_be(desc, logical=None):
+    """The column orders as big-endian two's complement: a FIXED_LEN_BYTE_ARRAY with
+    abi.COL_SIGNED_BE, or with a DECIMAL logical type."""
+    if desc.physical_type != abi.FIXED_LEN_BYTE_ARRAY:
+        return False
+    return bool(desc.flags & abi.COL_SIGNED_BE) or (logical is not None and logical.kind == abi.LT_DECIMAL)
+
+
+def literal(desc, value, logical=None):
     """`value` as the bytes pqg_filter takes for a column of this description (its physical
-    little-endian layout).  ValueError when the value does not fit the type."""
+    little-endian layout).  With the column's `logical` type: a decimal.Decimal or int on a
+    DECIMAL column is the scaled integer (type_length big-endian bytes for FLBA, the int32 / int64
+    for integer-backed decimals), a datetime / np.datetime64 on a TIMESTAMP column and a date on a
+    DATE column the integer in the column's unit.  ValueError when the value does not fit the
+    type or is not exact at the column's scale or unit."""
+    from .logical import typed_literal
+    typed = typed_literal(desc, value, logical)
+    if typed is not None:
+        return typed
     t = desc.physical_type
     if t in _NUM:
         fmt = _NUM[t][1 if desc.flags & abi.COL_UNSIGNED else 0]
@@ -113,9 +134,10 @@ def literal(desc, value):
     raise ValueError("no literal for physical type %d" % t)
 
 
-def compare(desc, a, b):
+def compare(desc, a, b, logical=None):
     """pqg_filter's order of two values given as physical bytes: -1, 0, 1, or None when they are
-    unordered (a NaN) or not values of the type (a wrong length)."""
+    unordered (a NaN) or not values of the type (a wrong length).  A FIXED_LEN_BYTE_ARRAY that is
+    signed_be() orders as big-endian two's complement."""
     t = desc.physical_type
     if t in _NUM:
         fmt = _NUM[t][1 if desc.flags & abi.COL_UNSIGNED else 0]
@@ -134,15 +156,17 @@ def compare(desc, a, b):
         if desc.type_length < 1 or len(a) != desc.type_length or len(b) != desc.type_length:
             return None
         x, y = bytes(a), bytes(b)
+        if signed_be(desc, logical):
+            x, y = bytes([x[0] ^ 0x80]) + x[1:], bytes([y[0] ^ 0x80]) + y[1:]
     else:
         return None
     return -1 if x < y else 1 if x > y else 0
 
 
-def _rules_out(desc, op, lit, lo, hi):
+def _rules_out(desc, op, lit, lo, hi, logical=None):
     """No value in [lo, hi] passes `op lit` (all as physical bytes); False when in doubt."""
     is_float = desc.physical_type in (abi.FLOAT, abi.DOUBLE)
-    c_lo, c_hi = compare(desc, lo, lit), compare(desc, hi, lit)  # bound against the literal
+    c_lo, c_hi = compare(desc, lo, lit, logical), compare(desc, hi, lit, logical)  # bound against the literal
     if c_lo is None or c_hi is None:
         return False
     if op == abi.OP_EQ:
@@ -160,10 +184,11 @@ def _rules_out(desc, op, lit, lo, hi):
     return False
 
 
-def term_rules_out(desc, term, stats, rows):
+def term_rules_out(desc, term, stats, rows, logical=None):
     """The statistics of a chunk of `rows` rows show that no row passes `term`.  stats: (min bytes
     or None, max bytes or None, null_count or -1).  Conservative: a missing or odd statistic
-    rules nothing out."""
+    rules nothing out.  logical: the column's abi.LogicalType, for typed literals and the signed
+    order of FLBA decimals; with it a BYTE_ARRAY decimal's statistics rule nothing out."""
     lo, hi, nulls = stats
     if desc.max_rep > 0 or rows <= 0:
         return False
@@ -177,6 +202,8 @@ def term_rules_out(desc, term, stats, rows):
         return False
     if lo is None or hi is None:
         return False
+    if logical is not None and logical.kind == abi.LT_DECIMAL and desc.physical_type == abi.BYTE_ARRAY:
+        return False  # values of different lengths: neither byte order is the numeric one
     if desc.physical_type in (abi.FLOAT, abi.DOUBLE):
         # a NaN bound says nothing; writers disagree on the sign of a zero bound
         fmt = _NUM[desc.physical_type][0]
@@ -189,14 +216,14 @@ def term_rules_out(desc, term, stats, rows):
             lo = struct.pack(fmt, -0.0)
         if y == 0:
             hi = struct.pack(fmt, 0.0)
-    c = compare(desc, lo, hi)
+    c = compare(desc, lo, hi, logical)
     if c is None or c > 0:
         return False
     try:
         if term.op == "in":
-            return all(_rules_out(desc, abi.OP_EQ, literal(desc, v), lo, hi) for v in term.values)
+            return all(_rules_out(desc, abi.OP_EQ, literal(desc, v, logical), lo, hi, logical) for v in term.values)
         if term.op == "not in":
-            return any(_rules_out(desc, abi.OP_NE, literal(desc, v), lo, hi) for v in term.values)
-        return _rules_out(desc, term.op, literal(desc, term.values), lo, hi)
+            return any(_rules_out(desc, abi.OP_NE, literal(desc, v, logical), lo, hi, logical) for v in term.values)
+        return _rules_out(desc, term.op, literal(desc, term.values, logical), lo, hi, logical)
     except (ValueError, TypeError, AttributeError):
         return False

@@ -73,6 +73,14 @@ class ParquetFile:
             ci = abi.ColumnInfo()
             _check(L.pqg_file_column(h, i, C.byref(ci)), "pqg_file_column")
             self.columns.append(ci)
+        self.logical_types = []  # abi.LogicalType per column, parallel to `columns`
+        # an older library named by PQG_LIB (A/B runs against a parent's build) has no logical types
+        known = hasattr(L, "pqg_file_column_logical")
+        for i in range(self.num_columns):
+            lt = abi.LogicalType(converted_type=-1)
+            if known:
+                _check(L.pqg_file_column_logical(h, i, C.byref(lt)), "pqg_file_column_logical")
+            self.logical_types.append(lt)
         self.schema_nodes = []  # depth first, below the root (pqg_file_schema_node)
         for i in range(L.pqg_file_num_schema_nodes(h)):
             sn = abi.SchemaNode()
@@ -207,11 +215,18 @@ class DecodedColumn:
 
     A chunk decoded with abi.COL_KEEP_DICT holds its `dictionary` (None when materialised):
     values are then num_values little-endian int32 keys and value_width is 4; materialize()
-    gives the column as the decode without the flag lays it out."""
+    gives the column as the decode without the flag lays it out.
+
+    `logical` is the column's abi.LogicalType when the reader ran with convert_logical (None
+    otherwise): DECIMAL values (or dictionary entries) are then 16 / 32 little-endian
+    two's-complement bytes and INT96 values int64 in the reader's int96_unit, unless the column
+    could not be converted (a precision outside 1..76, an FLBA wider than the output) and came
+    back raw."""
 
     def __init__(self, status, error_page, num_slots, num_values, value_width, def_levels, rep_levels, values,
-                 pages, offsets=None, dictionary=None):
+                 pages, offsets=None, dictionary=None, logical=None):
         self.dictionary = dictionary
+        self.logical = logical
         self.status = status
         self.error_page = error_page
         self.num_slots = num_slots
@@ -236,7 +251,7 @@ class DecodedColumn:
             return self
         vals, offs = d.lookup(self.keys())
         return DecodedColumn(self.status, self.error_page, self.num_slots, self.num_values, d.value_width,
-                             self.def_levels, self.rep_levels, vals, self.pages, offs)
+                             self.def_levels, self.rep_levels, vals, self.pages, offs, logical=self.logical)
 
 
 class GpuDecoder:
@@ -530,6 +545,58 @@ class GpuDecoder:
         _check(self.L.pqg_last_filter_ms(self.ctx, C.byref(ms)), "pqg_last_filter_ms")
         return ms.value
 
+    # ---- K10: logical-type conversion
+    def convert(self, values_ptr, num_values, values_bytes, kind, in_width, out_width, unit=abi.UNIT_NONE,
+                offsets_ptr=None):
+        """pqg_convert on device values (abi.CONV_*): decimals to out_width (16 / 32) little-endian
+        bytes, INT96 to int64 in `unit` (abi.UNIT_*).  offsets_ptr: the int64 offsets of BYTE_ARRAY
+        decimals (in_width 0).  Returns the device pointer of the num_values * out_width output
+        bytes, allocated here: the caller frees it (free).  A BYTE_ARRAY decimal of length 0 or
+        above out_width raises PqgError(SIZE) with the count in its `num_bad`."""
+        a = abi.ConvertArgs()
+        a.values, a.offsets = values_ptr or None, offsets_ptr or None
+        a.num_values, a.values_bytes = num_values, values_bytes
+        a.kind, a.in_width, a.out_width, a.unit = kind, in_width, out_width, unit
+        a.out = self.alloc(num_values * out_width)
+        rc = self.L.pqg_convert(self.ctx, C.byref(a))
+        if rc != 0:
+            self.free(a.out)
+            e = PqgError(rc, "pqg_convert")
+            e.num_bad = int(a.num_bad)
+            raise e
+        return a.out
+
+    def last_convert_ms(self):
+        ms = C.c_float()
+        _check(self.L.pqg_last_convert_ms(self.ctx, C.byref(ms)), "pqg_last_convert_ms")
+        return ms.value
+
+    def convert_dictionary(self, job_index, cv):
+        """The dictionary of job `job_index` (dictionary()) with its entries converted on the device
+        by `cv` (a pqgpu.logical.Conversion): values are count * out_width bytes, value_width the
+        output width.  Entries the page does not hold and the nil entry are what zero bytes convert
+        to; nil_entry is then -1."""
+        from .logical import int96_zero
+        d = abi.Dictionary()
+        _check(self.L.pqg_get_dictionary(self.ctx, job_index, C.byref(d)), "pqg_get_dictionary")
+        ow, n = cv.out_width, int(d.count)
+        held = n if cv.in_width == 0 else min(n, int(d.values_bytes) // cv.in_width)
+        vals = np.zeros(n * ow, np.uint8)
+        if held > 0:
+            out = self.convert(d.values, held, d.values_bytes, cv.kind, cv.in_width, ow, cv.unit,
+                               d.offsets if cv.in_width == 0 else None)
+            try:
+                vals[:held * ow] = self.d2h(out, held * ow)
+            finally:
+                self.free(out)
+        if cv.kind == abi.CONV_INT96_TIME:
+            zero = np.frombuffer(np.int64(int96_zero(cv.unit)).tobytes(), np.uint8)
+            t = vals.reshape(n, ow)
+            t[held:] = zero
+            if 0 <= d.nil_entry < n:
+                t[d.nil_entry] = zero
+        return Dictionary(vals, None, n, ow, -1, d.page)
+
     def download_nested(self, a, chars=None, physical_type=None, flags=0, dictionary=None):
         """The outputs of an assemble_nested call as a NestedColumn on the host
         (`chars`: the decoded chars of a byte-array leaf, already downloaded; `dictionary`:
@@ -693,9 +760,25 @@ class FileReader:
     read_row_group_nested decode their chunks with abi.COL_KEEP_DICT (int32 keys plus a
     Dictionary instead of values).  A chunk with a data page that is not dictionary encoded is
     decoded again without the flag and comes back materialised (dictionary None).  BOOLEAN
-    columns are never flagged; next_row ignores the option, rows need values."""
+    columns are never flagged; next_row ignores the option, rows need values.
+    `convert_logical`: read_row_group (filtered or not) and read_row_group_nested convert, on the
+    GPU before the download (pqg_convert; after pqg_select in a filtered read), DECIMAL leaves of
+    precision 1..76 on FLBA (type_length up to the output width) / BYTE_ARRAY / INT32 / INT64 to 16
+    (precision <= 38) or 32 little-endian two's-complement bytes, and INT96 leaves to int64 in
+    `int96_unit` ("s", "ms", "us", "ns"); every DecodedColumn then carries its column's
+    abi.LogicalType in `logical`, and a leaf that cannot be converted comes back raw.  Of a column
+    that keeps its dictionary only the dictionary's entries are converted.  Filters then take
+    typed literals (pqgpu.filters.literal), order FLBA decimals signed, and compare an INT96 column
+    as int64 nanoseconds since the epoch (such a predicate column is decoded materialised, whatever
+    read_dictionary says); a predicate on a BYTE_ARRAY decimal raises PqgError(UNSUPPORTED).
+    next_row ignores the option.  Off (the default), every method returns what it always did."""
 
-    def __init__(self, source, *columns, device=0, decoder=None, verify_crc=False, read_dictionary=()):
+    def __init__(self, source, *columns, device=0, decoder=None, verify_crc=False, read_dictionary=(),
+                 convert_logical=False, int96_unit="ns"):
+        if int96_unit not in abi.UNITS:
+            raise ValueError("int96_unit: one of %s" % ", ".join(sorted(abi.UNITS)))
+        self.convert_logical = bool(convert_logical)
+        self.int96_unit = abi.UNITS[int96_unit]
         self.file = ParquetFile.open(source) if isinstance(source, (str, os.PathLike)) else ParquetFile(source)
         self.dec = decoder or GpuDecoder(device)
         if verify_crc:
@@ -726,6 +809,46 @@ class FileReader:
             if any(path == p or path.startswith(p + ".") for p in columns):
                 out.append(i)
         return out
+
+    def _logical(self, c):
+        """Column c's abi.LogicalType when convert_logical is on, else None."""
+        return self.file.logical_types[c] if self.convert_logical else None
+
+    def _conversion(self, c):
+        """Column c's pqgpu.logical.Conversion, None when it stays as it is."""
+        if not self.convert_logical:
+            return None
+        from .logical import conversion
+        return conversion(self.file.columns[c].desc, self.file.logical_types[c], self.int96_unit)
+
+    def _convert_values(self, cv, values, num_values, values_bytes, offsets):
+        """pqg_convert of dense device values by `cv`, downloaded."""
+        out = self.dec.convert(values, num_values, values_bytes, cv.kind, cv.in_width, cv.out_width, cv.unit,
+                               offsets if cv.in_width == 0 else None)
+        try:
+            return self.dec.d2h(out, num_values * cv.out_width)
+        finally:
+            self.dec.free(out)
+
+    def _download(self, r, i, c):
+        """Job i's result (column c) on the host, converted when convert_logical asks for it."""
+        cv = self._conversion(c)
+        if cv is None or r.status != 0:
+            col = self.dec.download(r, i)
+        else:
+            dec = self.dec
+            lv_def = dec.d2h(r.def_levels, r.num_slots) if r.def_levels else None
+            lv_rep = dec.d2h(r.rep_levels, r.num_slots) if r.rep_levels else None
+            if r.col_flags & abi.COL_KEEP_DICT:  # the keys as they are, the dictionary's entries converted
+                col = DecodedColumn(r.status, r.error_page, r.num_slots, r.num_values, r.value_width, lv_def, lv_rep,
+                                    dec.d2h(r.values, r.values_bytes), dec.pages(i), None,
+                                    dictionary=dec.convert_dictionary(i, cv))
+            else:
+                vals = self._convert_values(cv, r.values, r.num_values, r.values_bytes, r.offsets)
+                col = DecodedColumn(r.status, r.error_page, r.num_slots, r.num_values, cv.out_width, lv_def, lv_rep,
+                                    vals, dec.pages(i), None)
+        col.logical = self._logical(c)
+        return col
 
     def row_group_count(self):
         return self.file.num_row_groups
@@ -767,7 +890,7 @@ class FileReader:
         res, dev, nbytes = decode_spans(self.file, specs, self.dec, self.keep_dict)
         self.uploaded_bytes += nbytes
         try:
-            return {self.file.columns[c].path.decode(): self.dec.download(r, i)
+            return {self.file.columns[c].path.decode(): self._download(r, i, c)
                     for i, ((_, c), r) in enumerate(zip(specs, res))}
         finally:
             self.dec.free(dev)
@@ -792,9 +915,19 @@ class FileReader:
             if self.file.columns[c].desc.max_rep > 0:
                 raise PqgError(abi.STATUS_CODES["UNSUPPORTED"], "filtered read of the repeated column %s"
                                % self.file.columns[c].path.decode())
+        keep_named = self._dict_named
+        if self.convert_logical:
+            for c in pred_cols:
+                d, lt = self.file.columns[c].desc, self.file.logical_types[c]
+                if d.physical_type == abi.BYTE_ARRAY and lt.kind == abi.LT_DECIMAL:
+                    raise PqgError(abi.STATUS_CODES["UNSUPPORTED"], "predicate on the BYTE_ARRAY decimal column %s"
+                                   % self.file.columns[c].path.decode())
+            # an INT96 predicate column is compared as converted int64 values: decoded materialised
+            keep_named = frozenset(c for c in keep_named if not (
+                c in pred_cols and self.file.columns[c].desc.physical_type == abi.INT96))
         self._release()
         specs = [(rg, c) for c in cols]
-        res, dev, nbytes = decode_spans(self.file, specs, self.dec, self._dict_named)
+        res, dev, nbytes = decode_spans(self.file, specs, self.dec, keep_named)
         self.uploaded_bytes += nbytes
         job = {c: i for i, c in enumerate(cols)}
         temps = []
@@ -807,17 +940,33 @@ class FileReader:
                 raise PqgError(abi.STATUS_CODES["INVALID_ARG"], "row group %d: columns of different lengths" % rg)
             bm_bytes = (rows + 31) // 32 * 4
             dicts = {}
+            as_ns = {}  # INT96 predicate columns (convert_logical): their values as int64 ns, on the device
 
             def run(term, bitmap, first_combine):
                 c = self.file.column_index(term.column)
-                r, desc = res[job[c]], self.file.columns[c].desc
+                r, desc, lt = res[job[c]], self.file.columns[c].desc, self._logical(c)
                 if r.col_flags & abi.COL_KEEP_DICT and c not in dicts:
                     d = abi.Dictionary()
                     _check(self.dec.L.pqg_get_dictionary(self.dec.ctx, job[c], C.byref(d)), "pqg_get_dictionary")
                     dicts[c] = d
+                values, values_bytes = r.values, r.values_bytes
+                if lt is not None and desc.physical_type == abi.INT96:
+                    if c not in as_ns:
+                        as_ns[c] = self.dec.convert(r.values, r.num_values, r.values_bytes, abi.CONV_INT96_TIME, 12, 8,
+                                                    abi.UNIT_NANOS)
+                        temps.append(as_ns[c])
+                    values, values_bytes = as_ns[c], r.num_values * 8
+                    desc = abi.ColumnDesc(abi.INT64, -1, desc.max_def, desc.max_rep, desc.codec, 0)
+                    lt = abi.LogicalType(kind=abi.LT_TIMESTAMP, unit=abi.UNIT_NANOS)
+                elif lt is not None and F.signed_be(desc, lt) and desc.type_length >= 1:
+                    desc = abi.ColumnDesc.from_buffer_copy(desc)
+                    desc.flags |= abi.COL_SIGNED_BE
                 for k, (op, val, comb) in enumerate(term.steps()):
-                    lit = F.literal(desc, val) if val is not None else None
-                    self.dec.filter_result(bitmap, r, desc, op, lit, first_combine if k == 0 else comb, dicts.get(c))
+                    lit = F.literal(desc, val, lt) if val is not None else None
+                    self.dec.filter(bitmap, desc, op, lit, def_ptr=r.def_levels, values_ptr=values,
+                                    offsets_ptr=r.offsets, num_rows=r.num_slots, num_values=r.num_values,
+                                    values_bytes=values_bytes, combine=first_combine if k == 0 else comb,
+                                    dictionary=dicts.get(c))
 
             def conj_bitmap(terms):
                 """One conjunction into a new device bitmap: the terms chain with AND; an `in`
@@ -855,19 +1004,28 @@ class FileReader:
                 desc = self.file.columns[c].desc
                 a = self.dec.select(bitmap, r.def_levels, r.values, r.offsets, rows, r.num_values, r.values_bytes,
                                     desc.max_def, r.value_width)
+                keep = bool(r.col_flags & abi.COL_KEEP_DICT)
+                cv = self._conversion(c)
+                width = r.value_width
                 try:
                     lv = self.dec.d2h(a.out_def_levels, a.rows_out) if desc.max_def > 0 else None
-                    vals = self.dec.d2h(a.out_values, a.bytes_out)
                     offs = None
-                    if r.value_width == 0:
-                        offs = self.dec.d2h(a.out_offsets, (a.values_out + 1) * 8, np.int64) if a.out_offsets \
-                            else np.zeros(1, np.int64)
+                    if cv is not None and not keep:  # only the selected values are converted
+                        vals = self._convert_values(cv, a.out_values, a.values_out, a.bytes_out, a.out_offsets)
+                        width = cv.out_width
+                    else:
+                        vals = self.dec.d2h(a.out_values, a.bytes_out)
+                        if r.value_width == 0:
+                            offs = self.dec.d2h(a.out_offsets, (a.values_out + 1) * 8, np.int64) if a.out_offsets \
+                                else np.zeros(1, np.int64)
                 finally:
                     self.dec.free_select(a)
-                keep = bool(r.col_flags & abi.COL_KEEP_DICT)
+                dic = None
+                if keep:
+                    dic = self.dec.convert_dictionary(i, cv) if cv is not None else self.dec.dictionary(i)
                 out[self.file.columns[c].path.decode()] = DecodedColumn(
-                    r.status, r.error_page, int(a.rows_out), int(a.values_out), r.value_width, lv, None, vals,
-                    self.dec.pages(i), offs, dictionary=self.dec.dictionary(i) if keep else None)
+                    r.status, r.error_page, int(a.rows_out), int(a.values_out), width, lv, None, vals,
+                    self.dec.pages(i), offs, dictionary=dic, logical=self._logical(c))
             return out
         finally:
             for p in temps:
@@ -878,7 +1036,9 @@ class FileReader:
         """The row groups whose footer statistics cannot rule out `filters` (as read_row_group
         takes them), in file order: a row group is dropped when every conjunction holds a term
         that no row of it can pass.  Conservative: a missing, truncated or odd statistic keeps the
-        row group; FLOAT / DOUBLE never prune on != / not in or on a NaN bound.  Host only."""
+        row group; FLOAT / DOUBLE never prune on != / not in or on a NaN bound.  With convert_logical
+        the statistics of FLBA decimals order signed, literals may be typed, and an INT96 or
+        BYTE_ARRAY decimal column never prunes.  Host only."""
         from . import filters as F
         dnf = F.parse(filters)
         keep = []
@@ -891,7 +1051,10 @@ class FileReader:
                     st = self.file.chunk_stats(rg, c)
                 except PqgError:
                     return False
-                return F.term_rules_out(self.file.columns[c].desc, term, st, rows)
+                desc, lt = self.file.columns[c].desc, self._logical(c)
+                if lt is not None and desc.physical_type == abi.INT96:
+                    return False
+                return F.term_rules_out(desc, term, st, rows, lt)
 
             if not all(any(out(t) for t in terms) for terms in dnf):
                 keep.append(rg)
@@ -927,14 +1090,30 @@ class FileReader:
                 desc = self.file.columns[c].desc
                 ld, ed = thr[c]
                 # a leaf that kept its dictionary goes through as the 4-byte fixed-width leaf its keys are
-                dic = self.dec.dictionary(i) if r.col_flags & abi.COL_KEEP_DICT else None
-                a = self.dec.assemble_nested(r.def_levels, r.rep_levels, r.values, r.num_slots, desc.max_def, ld, ed,
-                                             value_width=r.value_width, value_offsets_ptr=r.offsets)
+                keep = bool(r.col_flags & abi.COL_KEEP_DICT)
+                cv = self._conversion(c)
+                values, width, offsets, ptype, flags, conv = r.values, r.value_width, r.offsets, desc.physical_type, \
+                    desc.flags, None
+                if cv is not None:
+                    ptype, flags = cv.physical_type, 0
+                    if not keep:  # the dense leaf values converted: a fixed-width leaf of the output width
+                        conv = self.dec.convert(r.values, r.num_values, r.values_bytes, cv.kind, cv.in_width,
+                                                cv.out_width, cv.unit, r.offsets if cv.in_width == 0 else None)
+                        values, width, offsets = conv, cv.out_width, None
                 try:
-                    chars = self.dec.d2h(r.values, r.values_bytes) if r.offsets else None
-                    out[path] = self.dec.download_nested(a, chars, desc.physical_type, desc.flags, dic)
+                    dic = None
+                    if keep:
+                        dic = self.dec.convert_dictionary(i, cv) if cv is not None else self.dec.dictionary(i)
+                    a = self.dec.assemble_nested(r.def_levels, r.rep_levels, values, r.num_slots, desc.max_def, ld, ed,
+                                                 value_width=width, value_offsets_ptr=offsets)
+                    try:
+                        chars = self.dec.d2h(r.values, r.values_bytes) if offsets else None
+                        out[path] = self.dec.download_nested(a, chars, ptype, flags, dic)
+                    finally:
+                        self.dec.free_nested(a)
                 finally:
-                    self.dec.free_nested(a)
+                    if conv is not None:
+                        self.dec.free(conv)
             return out
         finally:
             self.dec.free(dev)
