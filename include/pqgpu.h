@@ -526,9 +526,49 @@ typedef struct pqg_nested_args {
 } pqg_nested_args;
 int pqg_assemble_nested(pqg_ctx* ctx, pqg_nested_args* args);
 
+/* ---- K8 struct export: validity bitmaps of the structs on a leaf's path ------
+ * The nested export gives the lists and the leaf; this gives the structs (the
+ * groups that are neither lists nor maps) above the same leaf, up to
+ * PQG_MAX_STRUCTS of them a call, all from one read of the level streams.  A
+ * struct under R lists (R = 0..depth) that is present at def >= struct_def has,
+ * with elem_def[0] = 0 and elem_def as in pqg_nested_level, for slot i:
+ *   entry(i) = rep[i] <= R && def[i] >= elem_def[R]    one struct slot (R = 0: one per row)
+ *   valid(i) = def[i] >= struct_def
+ * valid's bit goes at rank entry(i); num_entries = #entry, null_count =
+ * #(entry && !valid).  Every level up to struct_def lies on the part of the
+ * path that all leaves below the struct share, so any of them gives the same
+ * bits.  A struct below a null ancestor struct still has its slot, with bit 0.
+ * validity NULL: the struct is only counted.  rep_levels NULL (depth 0 only):
+ * every rep is 0.  depth outside 0..PQG_MAX_LIST_DEPTH is PQG_ERR_UNSUPPORTED;
+ * PQG_ERR_INVALID_ARG: num_structs outside 0..PQG_MAX_STRUCTS, a struct's
+ * depth outside 0..depth, elem_def not strictly increasing or above max_def, a
+ * struct_def not in (elem_def[R], max_def] or (R < depth) not below
+ * elem_def[R+1], def_levels NULL with structs and slots, rep_levels NULL with
+ * depth > 0.  num_slots == 0 does nothing (all counts 0).  No output is
+ * written when the call fails.  Bitmaps are zeroed by the call and written as
+ * whole dwords; bits at and past num_entries are zero. */
+#define PQG_MAX_STRUCTS 8
+typedef struct pqg_struct_level {
+  int32_t depth;        /* lists above the struct on the path: 0 .. args.depth            */
+  int32_t struct_def;   /* the struct is present when def >= struct_def                   */
+  uint8_t* validity;    /* out, DEVICE, 4 * ceil(num_slots / 32) bytes, or NULL (count)   */
+  int64_t num_entries;  /* out: struct slots                                              */
+  int64_t null_count;   /* out                                                            */
+} pqg_struct_level;
+typedef struct pqg_struct_args {
+  const uint8_t *def_levels, *rep_levels;   /* DEVICE; rep NULL: every rep is 0           */
+  int64_t num_slots;
+  int32_t max_def, depth;                   /* depth = lists on the leaf's path (max_rep) */
+  int32_t elem_def[PQG_MAX_LIST_DEPTH];     /* as in pqg_nested_level                     */
+  int32_t num_structs, reserved;
+  pqg_struct_level st[PQG_MAX_STRUCTS];
+} pqg_struct_args;
+/* Enqueue the struct export on the ctx stream and wait; fills the counts. */
+int pqg_assemble_structs(pqg_ctx* ctx, pqg_struct_args* args);
+
 /* Device time (ms) of the K8 kernels of the last pqg_assemble /
- * pqg_assemble_list / pqg_assemble_nested call: HIP events on the ctx stream around its kernel
- * launches (the count read-back and host syncs excluded). */
+ * pqg_assemble_list / pqg_assemble_nested / pqg_assemble_structs call: HIP events on the ctx
+ * stream around its kernel launches (the count read-back and host syncs excluded). */
 int pqg_last_assemble_ms(pqg_ctx* ctx, float* ms);
 
 /* ---- K9s: row predicates and row selection (beyond the reference, which has no
@@ -738,6 +778,12 @@ int pqg_file_num_schema_nodes(const pqg_file* f);
 /* PQG_ERR_METADATA when the node's name does not fit pqg_schema_node.name (a
  * truncated name would be a different map key than the reference's) */
 int pqg_file_schema_node(const pqg_file* f, int i, pqg_schema_node* out);
+/* The annotation of schema node i (the index of pqg_file_schema_node): PQG_NODE_LIST for
+ * LogicalType LIST or converted type LIST (3), PQG_NODE_MAP for LogicalType MAP or converted
+ * type MAP (1) / MAP_KEY_VALUE (2), PQG_NODE_PLAIN for everything else, leaves included.  A
+ * LogicalType LIST or MAP wins over the converted type.  A negative status on a bad index. */
+enum { PQG_NODE_PLAIN = 0, PQG_NODE_LIST = 1, PQG_NODE_MAP = 2 };
+int pqg_file_schema_node_kind(const pqg_file* f, int i);
 
 /* ======================= oracle (TEST INFRASTRUCTURE) ===================== */
 /* Implemented only by oracle/liboracle.so.  Host pointers everywhere. */

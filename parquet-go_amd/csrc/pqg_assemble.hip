@@ -658,6 +658,212 @@ int nested_write_launch(hipStream_t s, const pqg_nested_args* a, int64_t* seg_sc
 }
 
 // ---------------------------------------------------------------------------
+// Struct export (pqg_assemble_structs): the validity bitmaps of the structs on
+// a leaf's path.  A struct under R lists has one slot per depth-R element
+// (e_R of the nested export; R = 0: per row), valid when def >= struct_def.
+// Its slots therefore rank exactly as e_R does, so the structs of a call share
+// the K + 1 ranks of their depths and differ only in the threshold: the
+// counters per segment are e_0..e_4 (zero past K) and the nulls of each struct
+// (kStructC of them, scanned by k_nest_scan), and the write pass packs every
+// struct's valid bit into one word per lane, compresses that word to rank
+// order once per depth in use (one ds_permute carries all structs of the
+// depth) and takes one ballot per struct from it.  Masks and bases are wave
+// uniform; per lane the pass holds the two levels, the packed bits and one
+// rank and one permuted word per depth.  Bitmap words are shared between
+// neighbouring waves (a segment's slots start at any bit), hence the atomic OR
+// into the zeroed bitmap, as for the list validity above.
+// ---------------------------------------------------------------------------
+constexpr int kStructC = PQG_MAX_LIST_DEPTH + 1 + PQG_MAX_STRUCTS;
+struct StructThr {
+  int ns, used;                  // structs; bit k of used: some struct sits at depth k
+  int depth[PQG_MAX_STRUCTS], sdef[PQG_MAX_STRUCTS];
+};
+struct StructOut {
+  uint32_t* validity[PQG_MAX_STRUCTS];
+};
+
+template <int K>
+__global__ void __launch_bounds__(256) k_struct_count(const uint8_t* def_, const uint8_t* rep_, int64_t n, int max_def,
+                                                      NestThr th, StructThr st, int64_t nseg, int64_t* seg_cnt) {
+  const PQG_G uint8_t* def = gconst(def_);
+  const PQG_G uint8_t* rep = gconst(rep_);
+  const int64_t seg = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (seg >= nseg) return;
+  const int lane = lane64();
+  const int64_t s0 = seg * kAsmSeg, s1 = s0 + kAsmSeg < n ? s0 + kAsmSeg : n;
+  int cnt[kStructC];
+#pragma unroll
+  for (int j = 0; j < kStructC; j++) cnt[j] = 0;
+  auto count = [&](const NestPred<K>& p) {  // one 64-slot ballot
+    uint64_t m[K + 1];
+#pragma unroll
+    for (int k = 0; k <= K; k++) {
+      m[k] = ballot64(p.e[k]);
+      cnt[k] += __popcll(m[k]);
+    }
+#pragma unroll
+    for (int s = 0; s < PQG_MAX_STRUCTS; s++)
+      if (s < st.ns) {
+        const uint64_t below = ballot64(p.d < st.sdef[s]);
+#pragma unroll
+        for (int k = 0; k <= K; k++)  // the struct's depth is wave uniform: one of these branches runs
+          if (st.depth[s] == k) cnt[PQG_MAX_LIST_DEPTH + 1 + s] += __popcll(m[k] & below);
+      }
+  };
+  int64_t b = s0;
+  // a dword of each stream per lane, as in k_nest_count
+  if ((((uintptr_t)def_ | (uintptr_t)rep_) & 3) == 0) {
+    for (; b + 256 <= s1; b += 256) {
+      const int64_t q = (b >> 2) + lane;
+      const uint32_t dw = ((const PQG_G uint32_t*)def)[q];
+      const uint32_t rw = rep ? ((const PQG_G uint32_t*)rep)[q] : 0u;
+#pragma unroll
+      for (int j = 0; j < 4; j++)
+        count(nest_pred_of<K>((int)((dw >> (8 * j)) & 0xffu), (int)((rw >> (8 * j)) & 0xffu), max_def, th));
+    }
+  }
+  for (; b < s1; b += 64) count(nest_pred<K>(def, rep, b + lane, b + lane < s1, max_def, th));
+  if (lane == 0) {
+    PQG_G int64_t* o = gmut(seg_cnt) + kStructC * seg;
+#pragma unroll
+    for (int j = 0; j < kStructC; j++) o[j] = cnt[j];
+  }
+}
+
+template <int K>
+__global__ void __launch_bounds__(256) k_struct_write(const uint8_t* def_, const uint8_t* rep_, int64_t n, int max_def,
+                                                      NestThr th, StructThr st, int64_t nseg, const int64_t* seg_cnt,
+                                                      StructOut out) {
+  const PQG_G uint8_t* def = gconst(def_);
+  const PQG_G uint8_t* rep = gconst(rep_);
+  const int64_t seg = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (seg >= nseg) return;
+  const int lane = lane64();
+  const uint64_t lt = lane ? (~0ull >> (64 - lane)) : 0ull;
+  const int64_t s0 = seg * kAsmSeg, s1 = s0 + kAsmSeg < n ? s0 + kAsmSeg : n;
+  const PQG_G int64_t* sc = gconst(seg_cnt) + kStructC * seg;
+  int64_t base[K + 1];  // elements of each depth before this ballot
+#pragma unroll
+  for (int k = 0; k <= K; k++) base[k] = sc[k];
+  // one 64-slot ballot: this lane's slot has predicates p (outside the segment d = -1: no bit)
+  auto emit = [&](const NestPred<K>& p) {
+    uint64_t m[K + 1];
+#pragma unroll
+    for (int k = 0; k <= K; k++) m[k] = ballot64(p.e[k]);
+    int vbits = 0;  // bit s: struct s is present at this slot
+#pragma unroll
+    for (int s = 0; s < PQG_MAX_STRUCTS; s++)
+      if (s < st.ns) vbits |= (int)(p.d >= st.sdef[s]) << s;
+    int got[K + 1];  // the vbits of the lane-th depth-k element of this ballot (compress_ballot's move)
+#pragma unroll
+    for (int k = 0; k <= K; k++) {
+      got[k] = 0;
+      if ((st.used >> k) & 1) {
+        const int rank = p.e[k] ? __popcll(m[k] & lt) : __popcll(m[k]) + __popcll(~m[k] & lt);
+        got[k] = __builtin_amdgcn_ds_permute(rank << 2, vbits);
+      }
+    }
+#pragma unroll
+    for (int s = 0; s < PQG_MAX_STRUCTS; s++) {
+      if (s < st.ns && out.validity[s]) {
+#pragma unroll
+        for (int k = 0; k <= K; k++) {  // the struct's depth is wave uniform: one of these branches runs
+          if (st.depth[s] == k) {
+            const uint64_t bits = ballot64(lane < __popcll(m[k]) && ((got[k] >> s) & 1));
+            if (lane == 0) or_bits(out.validity[s], base[k], bits);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int k = 0; k <= K; k++) base[k] += __popcll(m[k]);
+  };
+  int64_t b = s0;
+  // a dword of each stream per lane, handed round as in k_nest_write
+  if ((((uintptr_t)def_ | (uintptr_t)rep_) & 3) == 0) {
+    for (; b + 256 <= s1; b += 256) {
+      const int64_t q = (b >> 2) + lane;
+      const int dw = (int)((const PQG_G uint32_t*)def)[q];
+      const int rw = rep ? (int)((const PQG_G uint32_t*)rep)[q] : 0;
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        const int from = (16 * j + (lane >> 2)) << 2, sh = 8 * (lane & 3);
+        const int d = (__builtin_amdgcn_ds_bpermute(from, dw) >> sh) & 0xff;
+        const int r = (__builtin_amdgcn_ds_bpermute(from, rw) >> sh) & 0xff;
+        emit(nest_pred_of<K>(d, r, max_def, th));
+      }
+    }
+  }
+  for (; b < s1; b += 64) emit(nest_pred<K>(def, rep, b + lane, b + lane < s1, max_def, th));
+}
+
+static void struct_thresholds(const pqg_struct_args* a, NestThr* th, StructThr* st) {
+  for (int k = 0; k < PQG_MAX_LIST_DEPTH; k++) {
+    th->list_def[k] = 0;
+    th->elem_def[k] = k < a->depth ? a->elem_def[k] : 0;
+  }
+  st->ns = a->num_structs;
+  st->used = 0;
+  for (int s = 0; s < PQG_MAX_STRUCTS; s++) {
+    st->depth[s] = s < a->num_structs ? a->st[s].depth : 0;
+    st->sdef[s] = s < a->num_structs ? a->st[s].struct_def : 0;
+    if (s < a->num_structs) st->used |= 1 << a->st[s].depth;
+  }
+}
+
+// Count + scan of the struct export (num_slots > 0); tot[0..4] = e_0..e_4 (zero
+// past the depth), tot[5 + s] = nulls of struct s.  Writes no output.
+int struct_count_launch(hipStream_t s, const pqg_struct_args* a, int64_t* seg_scratch, int64_t* tot) {
+  const int64_t n = a->num_slots;
+  const int64_t nseg = (n + kAsmSeg - 1) / kAsmSeg;
+  const unsigned blocks = (unsigned)((nseg + 3) / 4);
+  NestThr th;
+  StructThr st;
+  struct_thresholds(a, &th, &st);
+#define PQG_SCNT(KK)                                                                                              \
+  hipLaunchKernelGGL(k_struct_count<KK>, dim3(blocks), dim3(256), 0, s, a->def_levels, a->rep_levels, n, a->max_def, \
+                     th, st, nseg, seg_scratch)
+  switch (a->depth) {
+    case 0: PQG_SCNT(0); break;
+    case 1: PQG_SCNT(1); break;
+    case 2: PQG_SCNT(2); break;
+    case 3: PQG_SCNT(3); break;
+    default: PQG_SCNT(4); break;
+  }
+#undef PQG_SCNT
+  hipLaunchKernelGGL(k_nest_scan<kStructC>, dim3(1), dim3(1024), 0, s, seg_scratch, nseg, tot);
+  return hipGetLastError() == hipSuccess ? PQG_OK : PQG_ERR_HIP;
+}
+
+// The bitmaps (num_slots > 0), after struct_count_launch.
+int struct_write_launch(hipStream_t s, const pqg_struct_args* a, const int64_t* seg_scratch) {
+  const int64_t n = a->num_slots;
+  const int64_t nseg = (n + kAsmSeg - 1) / kAsmSeg;
+  const unsigned blocks = (unsigned)((nseg + 3) / 4);
+  const size_t bm_bytes = (size_t)((n + 31) / 32) * 4;  // whole dwords (see pqgpu.h)
+  NestThr th;
+  StructThr st;
+  struct_thresholds(a, &th, &st);
+  StructOut out;
+  for (int j = 0; j < PQG_MAX_STRUCTS; j++) {
+    out.validity[j] = j < a->num_structs ? (uint32_t*)a->st[j].validity : nullptr;
+    if (out.validity[j]) hipMemsetAsync(out.validity[j], 0, bm_bytes, s);
+  }
+#define PQG_SWR(KK)                                                                                               \
+  hipLaunchKernelGGL(k_struct_write<KK>, dim3(blocks), dim3(256), 0, s, a->def_levels, a->rep_levels, n, a->max_def, \
+                     th, st, nseg, seg_scratch, out)
+  switch (a->depth) {
+    case 0: PQG_SWR(0); break;
+    case 1: PQG_SWR(1); break;
+    case 2: PQG_SWR(2); break;
+    case 3: PQG_SWR(3); break;
+    default: PQG_SWR(4); break;
+  }
+#undef PQG_SWR
+  return hipGetLastError() == hipSuccess ? PQG_OK : PQG_ERR_HIP;
+}
+
+// ---------------------------------------------------------------------------
 // ColumnStore refill: levels -> packedArray bytes (packed_array.go:34-101).
 // One lane per group of 8 levels: one 8-byte load, the 8 w-bit fields OR-ed
 // into a 64-bit word (bw <= 8 for u8 levels), bw byte stores.

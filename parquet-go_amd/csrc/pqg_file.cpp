@@ -32,6 +32,7 @@ struct Elem {
   bool has_scale = false, has_precision = false;
   int32_t scale = 0, precision = 0;
   pqg_logical_type lt;  // from the LogicalType union alone; kind PQG_LT_NONE without one that parses
+  int32_t group_lt = -1;  // PQG_NODE_* of the LogicalType union's member, -1 without one that parses
   std::string name;
   Elem() { memset(&lt, 0, sizeof(lt)); }
 };
@@ -193,6 +194,16 @@ struct Parser {
     });
     if (ok && q.c.pos == n) *out = lt;
   }
+  // LogicalType union: MAP (2) / LIST (3) or another member, the member set last wins; -1 when it does not parse
+  static int32_t group_annotation(const uint8_t* p, int64_t n) {
+    Parser q(p, n);
+    int32_t kind = -1;
+    const bool ok = q.fields([&](int t, int id) -> int {
+      if (t == T_STRUCT) kind = id == 2 ? PQG_NODE_MAP : id == 3 ? PQG_NODE_LIST : PQG_NODE_PLAIN;
+      return 0;
+    });
+    return ok && q.c.pos == n ? kind : -1;
+  }
   bool elem(Elem* e) {
     return fields([&](int t, int id) -> int {
       int32_t v;
@@ -212,6 +223,7 @@ struct Parser {
             const int64_t s0 = c.pos;
             if (!logical_unsigned(&e->unsigned_int)) return -1;
             logical(c.src.p + s0, c.pos - s0, &e->lt);
+            e->group_lt = group_annotation(c.src.p + s0, c.pos - s0);
             return 1;
           }
           break;
@@ -297,6 +309,7 @@ struct Parser {
 struct SNode {
   std::string name;
   int32_t rep, num_children, leaf, max_def, max_rep;
+  int32_t kind = PQG_NODE_PLAIN;  // PQG_NODE_*: the group's LIST / MAP annotation
 };
 
 struct pqg_file {
@@ -321,7 +334,11 @@ bool read_schema(const std::vector<Elem>& s, size_t& idx, const std::string& nam
     if (e.has_rep && e.rep != 0) d++;
     if (e.has_rep && e.rep == 2) r++;
     std::string nm = name.empty() ? e.name : name + "." + e.name;
-    nodes.push_back(SNode{e.name, e.has_rep ? e.rep : 0, e.num_children, -1, d, r});
+    int32_t kind = PQG_NODE_PLAIN;  // the LogicalType's LIST / MAP, else the converted type's
+    if (e.group_lt > PQG_NODE_PLAIN) kind = e.group_lt;
+    else if (e.has_ct && e.converted == 3) kind = PQG_NODE_LIST;
+    else if (e.has_ct && (e.converted == 1 || e.converted == 2)) kind = PQG_NODE_MAP;
+    nodes.push_back(SNode{e.name, e.has_rep ? e.rep : 0, e.num_children, -1, d, r, kind});
     idx++;
     for (int i = 0; i < e.num_children; i++)
       if (!read_schema(s, idx, nm, d, r, out, depth + 1, nodes)) return false;
@@ -501,6 +518,11 @@ int pqg_file_schema_node(const pqg_file* f, int i, pqg_schema_node* out) {
   out->max_def = n.max_def;
   out->max_rep = n.max_rep;
   return PQG_OK;
+}
+
+int pqg_file_schema_node_kind(const pqg_file* f, int i) {
+  if (!f || i < 0 || i >= (int)f->nodes.size()) return PQG_ERR_INVALID_ARG;
+  return f->nodes[(size_t)i].kind;
 }
 
 int pqg_file_column(const pqg_file* f, int col, pqg_column_info* out) {

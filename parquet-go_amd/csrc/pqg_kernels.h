@@ -123,6 +123,8 @@ int list_count_launch(hipStream_t s, const pqg_list_args* a, int64_t* seg_scratc
 int list_write_launch(hipStream_t s, const pqg_list_args* a, int64_t* seg_scratch);
 int nested_count_launch(hipStream_t s, const pqg_nested_args* a, int64_t* seg_scratch, int64_t* tot);
 int nested_write_launch(hipStream_t s, const pqg_nested_args* a, int64_t* seg_scratch, const int64_t* tot);
+int struct_count_launch(hipStream_t s, const pqg_struct_args* a, int64_t* seg_scratch, int64_t* tot);
+int struct_write_launch(hipStream_t s, const pqg_struct_args* a, const int64_t* seg_scratch);
 int pack_levels_launch(hipStream_t s, const uint8_t* levels, int64_t n, int bw, uint8_t* packed);
 int filter_launch(hipStream_t s, const flt::Pred& p, const flt::Col& c, const pqg_dictionary* dict, uint32_t* ebits,
                   uint8_t* bitmap, int64_t n, int mode, bool lds, int64_t* seg, int64_t* tot);

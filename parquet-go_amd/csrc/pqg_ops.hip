@@ -307,6 +307,57 @@ int pqg_assemble_nested(pqg_ctx* c, pqg_nested_args* a) {
   return write_pass(c, count_ms, [&] { return nested_write_launch(c->stream, a, seg, tot); });
 }
 
+// Struct export: the validity of the groups Column.getData (schema.go:235-264) returns as nil or as
+// a map, for up to PQG_MAX_STRUCTS structs above one leaf.
+int pqg_assemble_structs(pqg_ctx* c, pqg_struct_args* a) {
+  if (!c || !a) return PQG_ERR_INVALID_ARG;
+  if (a->depth < 0 || a->depth > PQG_MAX_LIST_DEPTH) return PQG_ERR_UNSUPPORTED;
+  if (a->num_slots < 0 || a->max_def < 0 || a->max_def > 255) return PQG_ERR_INVALID_ARG;
+  if (a->num_structs < 0 || a->num_structs > PQG_MAX_STRUCTS) return PQG_ERR_INVALID_ARG;
+  const int K = a->depth, ns = a->num_structs;
+  int ed[PQG_MAX_LIST_DEPTH + 1] = {0};  // ed[k]: elem_def of depth k, ed[0] = 0
+  for (int k = 1; k <= K; k++) {
+    ed[k] = a->elem_def[k - 1];
+    if (ed[k] <= ed[k - 1] || ed[k] > a->max_def) return PQG_ERR_INVALID_ARG;
+  }
+  for (int j = 0; j < ns; j++) {
+    const pqg_struct_level& s = a->st[j];
+    if (s.depth < 0 || s.depth > K) return PQG_ERR_INVALID_ARG;
+    if (s.struct_def <= ed[s.depth] || s.struct_def > a->max_def) return PQG_ERR_INVALID_ARG;
+    if (s.depth < K && s.struct_def >= ed[s.depth + 1]) return PQG_ERR_INVALID_ARG;
+  }
+  if (!a->def_levels && ns > 0 && a->num_slots > 0) return PQG_ERR_INVALID_ARG;
+  if (!a->rep_levels && K > 0) return PQG_ERR_INVALID_ARG;
+  if (a->num_slots == 0 || ns == 0) {  // nothing to read or nothing asked for
+    for (int j = 0; j < ns; j++) a->st[j].num_entries = a->st[j].null_count = 0;
+    c->k8_ms = 0.f;
+    return PQG_OK;
+  }
+  hipSetDevice(c->device);
+  constexpr int C = PQG_MAX_LIST_DEPTH + 1 + PQG_MAX_STRUCTS;
+  const int64_t nseg = (a->num_slots + 4095) / 4096;
+  if (c->asm_seg.grow((size_t)(C * nseg + C) * sizeof(int64_t))) return PQG_ERR_HIP;
+  int64_t* seg = (int64_t*)c->asm_seg.p;
+  int64_t* tot = seg + C * nseg;
+  int64_t h[C] = {0};
+  float count_ms = 0.f;
+  const int e = count_pass(c, c->ev_k8, [&] { return struct_count_launch(c->stream, a, seg, tot); }, tot, h, C, &count_ms);
+  if (e) return e;
+  bool any = false;
+  for (int j = 0; j < ns; j++) any = any || a->st[j].validity;
+  if (any) {
+    const int w = write_pass(c, count_ms, [&] { return struct_write_launch(c->stream, a, seg); });
+    if (w) return w;
+  } else {
+    c->k8_ms = count_ms;
+  }
+  for (int j = 0; j < ns; j++) {
+    a->st[j].num_entries = h[a->st[j].depth];
+    a->st[j].null_count = h[PQG_MAX_LIST_DEPTH + 1 + j];
+  }
+  return PQG_OK;
+}
+
 int pqg_last_assemble_ms(pqg_ctx* c, float* ms) {
   if (!c || !ms) return PQG_ERR_INVALID_ARG;
   *ms = c->k8_ms;

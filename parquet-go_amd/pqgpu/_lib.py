@@ -47,6 +47,7 @@ def lib():
         "pqg_assemble": ([P, C.POINTER(abi.AssembleArgs)], I),
         "pqg_assemble_list": ([P, C.POINTER(abi.ListArgs)], I),
         "pqg_assemble_nested": ([P, C.POINTER(abi.NestedArgs)], I),
+        "pqg_assemble_structs": ([P, C.POINTER(abi.StructArgs)], I),
         "pqg_last_assemble_ms": ([P, C.POINTER(C.c_float)], I),
         "pqg_decode_page": ([P, C.POINTER(abi.PageJob), C.POINTER(abi.ChunkResult)], I),
         "pqg_block_decompress": ([P, I, C.c_char_p, I64, P, I64, C.POINTER(I64)], I),
@@ -62,6 +63,7 @@ def lib():
         "pqg_file_chunk": ([P, I, I, C.POINTER(abi.ChunkMeta)], I),
         "pqg_file_num_schema_nodes": ([P], I),
         "pqg_file_schema_node": ([P, I, C.POINTER(abi.SchemaNode)], I),
+        "pqg_file_schema_node_kind": ([P, I], I),
         "pqg_file_chunk_stats": ([P, I, I, C.POINTER(abi.ChunkStats)], I),
         "pqg_filter": ([P, C.POINTER(abi.FilterArgs)], I),
         "pqg_select": ([P, C.POINTER(abi.SelectArgs)], I),
@@ -92,4 +94,5 @@ EXPORTED = [
     "pqg_file_column", "pqg_file_chunk", "pqg_file_num_schema_nodes", "pqg_file_schema_node",
     "pqg_get_dictionary", "pqg_file_chunk_stats", "pqg_filter", "pqg_select", "pqg_last_filter_ms",
     "pqg_convert", "pqg_last_convert_ms", "pqg_file_column_logical",
+    "pqg_assemble_structs", "pqg_file_schema_node_kind",
 ]

@@ -215,6 +215,26 @@ class NestedArgs(C.Structure):
                 ("num_rows", C.c_int64), ("num_leaf", C.c_int64), ("num_valid", C.c_int64)]
 
 
+MAX_STRUCTS = 8
+
+
+class StructLevel(C.Structure):
+    """pqg_struct_level (include/pqgpu.h, K8 struct export)."""
+    _fields_ = [("depth", C.c_int32), ("struct_def", C.c_int32), ("validity", C.c_void_p),
+                ("num_entries", C.c_int64), ("null_count", C.c_int64)]
+
+
+class StructArgs(C.Structure):
+    """pqg_struct_args (include/pqgpu.h, K8 struct export)."""
+    _fields_ = [("def_levels", C.c_void_p), ("rep_levels", C.c_void_p), ("num_slots", C.c_int64),
+                ("max_def", C.c_int32), ("depth", C.c_int32), ("elem_def", C.c_int32 * MAX_LIST_DEPTH),
+                ("num_structs", C.c_int32), ("reserved", C.c_int32), ("st", StructLevel * MAX_STRUCTS)]
+
+
+# pqg_file_schema_node_kind
+NODE_PLAIN, NODE_LIST, NODE_MAP = 0, 1, 2
+
+
 class ChunkStats(C.Structure):
     """pqg_chunk_stats (include/pqgpu.h): ColumnMetaData.statistics of one chunk."""
     _fields_ = [("min_value", C.c_void_p), ("max_value", C.c_void_p), ("min_len", C.c_int32),

@@ -51,9 +51,12 @@ def leaf_thresholds(schema_nodes, leaf):
     otherwise the list cannot be null and list_def[k] = elem_def[k-1]
     (elem_def[0] = 0).
 
-    Struct validity bitmaps are out of scope: a leaf under an optional struct
-    reports def == max_def as its validity, so a null struct and a null field
-    of a present struct both come out as a null leaf."""
+    Struct validity is not part of these thresholds: a leaf under an optional
+    struct reports def == max_def as its validity, so in this per-leaf view a
+    null struct and a null field of a present struct both come out as a null
+    leaf.  pqgpu.tree (FileReader.read_row_group_tree) tells them apart: it
+    adds the structs' own bitmaps (pqg_assemble_structs) and nests the leaves
+    under their structs, lists and maps."""
     list_def, elem_def = [], []
     level, prev_elem, optional_since = 0, 0, False
     for n in leaf_path(schema_nodes, leaf):

@@ -86,6 +86,9 @@ class ParquetFile:
             sn = abi.SchemaNode()
             _check(L.pqg_file_schema_node(h, i, C.byref(sn)), "pqg_file_schema_node")
             self.schema_nodes.append(sn)
+        # abi.NODE_* per schema node, parallel to `schema_nodes` (an older library named by PQG_LIB has none)
+        kinds = getattr(L, "pqg_file_schema_node_kind", None)
+        self.schema_kinds = [kinds(h, i) if kinds else abi.NODE_PLAIN for i in range(len(self.schema_nodes))]
 
     @classmethod
     def open(cls, path):
@@ -473,6 +476,47 @@ class GpuDecoder:
                  [x for k in range(a.depth) for x in (a.level[k].validity, a.level[k].offsets)]:
             if p:
                 self.free(p)
+
+    def assemble_structs(self, def_ptr, rep_ptr, num_slots, max_def, elem_def=(), structs=(), validity=True):
+        """K8 struct export of device level arrays: the validity bitmaps of up to abi.MAX_STRUCTS
+        structs above one leaf, `structs` = [(depth, struct_def)], elem_def as for
+        assemble_nested.  Allocates the bitmaps (validity=False: counts only) and returns the
+        StructArgs, whose st[j].validity are the device pointers (free_structs)."""
+        depth = len(elem_def)
+        if depth > abi.MAX_LIST_DEPTH:
+            raise PqgError(abi.STATUS_CODES["UNSUPPORTED"], "pqg_assemble_structs: %d list depths" % depth)
+        if len(structs) > abi.MAX_STRUCTS:
+            raise PqgError(abi.STATUS_CODES["INVALID_ARG"], "pqg_assemble_structs: %d structs" % len(structs))
+        a = abi.StructArgs()
+        a.def_levels, a.rep_levels = def_ptr or None, rep_ptr or None
+        a.num_slots, a.max_def, a.depth, a.num_structs = num_slots, max_def, depth, len(structs)
+        for k in range(depth):
+            a.elem_def[k] = elem_def[k]
+        bm = (num_slots + 31) // 32 * 4
+        for j, (d, sd) in enumerate(structs):
+            a.st[j].depth, a.st[j].struct_def = d, sd
+            a.st[j].validity = self.alloc(bm) if validity else None
+        try:
+            _check(self.L.pqg_assemble_structs(self.ctx, C.byref(a)), "pqg_assemble_structs")
+        except PqgError:
+            self.free_structs(a)
+            raise
+        return a
+
+    def free_structs(self, a):
+        """Free the bitmaps assemble_structs allocated."""
+        for j in range(a.num_structs):
+            if a.st[j].validity:
+                self.free(a.st[j].validity)
+
+    def download_structs(self, a):
+        """[(validity uint32 words or None, null_count, num_entries)] of an assemble_structs call."""
+        out = []
+        for j in range(a.num_structs):
+            s = a.st[j]
+            val = self.d2h(s.validity, (s.num_entries + 31) // 32 * 4, np.uint32) if s.validity else None
+            out.append((val, int(s.null_count), int(s.num_entries)))
+        return out
 
     def last_assemble_ms(self):
         ms = C.c_float()
@@ -1081,40 +1125,87 @@ class FileReader:
             thr[c] = (ld, ed)
         res, dev, nbytes = decode_spans(self.file, specs, self.dec, self.keep_dict)
         self.uploaded_bytes += nbytes
-        out = {}
+        try:
+            return {self.file.columns[c].path.decode(): self._nested_leaf(rg, i, c, r, thr[c])
+                    for i, ((_, c), r) in enumerate(zip(specs, res))}
+        finally:
+            self.dec.free(dev)
+
+    def _nested_leaf(self, rg, i, c, r, thr, lists=True):
+        """Job i's result (column c, thresholds thr) through pqg_assemble_nested, downloaded as a
+        NestedColumn; lists=False leaves the list depths' offsets and validity on the device."""
+        path = self.file.columns[c].path.decode()
+        if r.status != 0:
+            raise PqgError(r.status, "column %s of row group %d" % (path, rg))
+        desc = self.file.columns[c].desc
+        ld, ed = thr
+        # a leaf that kept its dictionary goes through as the 4-byte fixed-width leaf its keys are
+        keep = bool(r.col_flags & abi.COL_KEEP_DICT)
+        cv = self._conversion(c)
+        values, width, offsets, ptype, flags, conv = r.values, r.value_width, r.offsets, desc.physical_type, \
+            desc.flags, None
+        if cv is not None:
+            ptype, flags = cv.physical_type, 0
+            if not keep:  # the dense leaf values converted: a fixed-width leaf of the output width
+                conv = self.dec.convert(r.values, r.num_values, r.values_bytes, cv.kind, cv.in_width,
+                                        cv.out_width, cv.unit, r.offsets if cv.in_width == 0 else None)
+                values, width, offsets = conv, cv.out_width, None
+        try:
+            dic = None
+            if keep:
+                dic = self.dec.convert_dictionary(i, cv) if cv is not None else self.dec.dictionary(i)
+            a = self.dec.assemble_nested(r.def_levels, r.rep_levels, values, r.num_slots, desc.max_def, ld, ed,
+                                         value_width=width, value_offsets_ptr=offsets, validity=lists,
+                                         offsets=lists)
+            try:
+                chars = self.dec.d2h(r.values, r.values_bytes) if offsets else None
+                return self.dec.download_nested(a, chars, ptype, flags, dic)
+            finally:
+                self.dec.free_nested(a)
+        finally:
+            if conv is not None:
+                self.dec.free(conv)
+
+    def read_row_group_tree(self, rg):
+        """One row group's selected columns as one Arrow column tree (pqgpu.tree): a non-nullable
+        StructNode of `rows` slots whose children are the top-level fields, with structs, lists
+        and maps as the schema nests them (tree.plan).  One decode of the selected chunks; per
+        leaf one pqg_assemble_nested call; per representative leaf one pqg_assemble_structs call
+        for the nullable structs it stands for (several when there are more than
+        abi.MAX_STRUCTS).  Only Arrow buffers are downloaded: no level leaves the device.
+        read_dictionary and convert_logical apply to the leaves as in read_row_group_nested; a
+        chunk that fails raises the same PqgError, a leaf under more than abi.MAX_LIST_DEPTH lists
+        PqgError(UNSUPPORTED) before any GPU work."""
+        from . import tree
+        from .nested import leaf_thresholds
+        root = tree.plan(self.file.schema_nodes, self.file.schema_kinds, self.selected)
+        rows = self.file.row_group_rows(rg)
+        self._release()
+        specs = [(rg, c) for c in self.selected]
+        if not specs:
+            return tree.build(root, {}, {}, rows)
+        thr = {c: leaf_thresholds(self.file.schema_nodes, c) for _, c in specs}
+        by_leaf, with_lists = tree.structs_by_leaf(root), tree.list_leaves(root)
+        res, dev, nbytes = decode_spans(self.file, specs, self.dec, self.keep_dict)
+        self.uploaded_bytes += nbytes
+        columns, structs, info = {}, {}, {}
         try:
             for i, ((_, c), r) in enumerate(zip(specs, res)):
-                path = self.file.columns[c].path.decode()
-                if r.status != 0:
-                    raise PqgError(r.status, "column %s of row group %d" % (path, rg))
-                desc = self.file.columns[c].desc
-                ld, ed = thr[c]
-                # a leaf that kept its dictionary goes through as the 4-byte fixed-width leaf its keys are
-                keep = bool(r.col_flags & abi.COL_KEEP_DICT)
+                columns[c] = self._nested_leaf(rg, i, c, r, thr[c], lists=c in with_lists)
                 cv = self._conversion(c)
-                values, width, offsets, ptype, flags, conv = r.values, r.value_width, r.offsets, desc.physical_type, \
-                    desc.flags, None
-                if cv is not None:
-                    ptype, flags = cv.physical_type, 0
-                    if not keep:  # the dense leaf values converted: a fixed-width leaf of the output width
-                        conv = self.dec.convert(r.values, r.num_values, r.values_bytes, cv.kind, cv.in_width,
-                                                cv.out_width, cv.unit, r.offsets if cv.in_width == 0 else None)
-                        values, width, offsets = conv, cv.out_width, None
-                try:
-                    dic = None
-                    if keep:
-                        dic = self.dec.convert_dictionary(i, cv) if cv is not None else self.dec.dictionary(i)
-                    a = self.dec.assemble_nested(r.def_levels, r.rep_levels, values, r.num_slots, desc.max_def, ld, ed,
-                                                 value_width=width, value_offsets_ptr=offsets)
+                info[c] = dict(logical=self.file.logical_types[c], converted=cv is not None, unit=self.int96_unit)
+                todo = by_leaf.get(c, [])
+                desc = self.file.columns[c].desc
+                for at in range(0, len(todo), abi.MAX_STRUCTS):
+                    part = todo[at:at + abi.MAX_STRUCTS]
+                    a = self.dec.assemble_structs(r.def_levels, r.rep_levels, r.num_slots, desc.max_def, thr[c][1],
+                                                  [(p.depth, p.struct_def) for p in part])
                     try:
-                        chars = self.dec.d2h(r.values, r.values_bytes) if offsets else None
-                        out[path] = self.dec.download_nested(a, chars, ptype, flags, dic)
+                        for p, st in zip(part, self.dec.download_structs(a)):
+                            structs[p.node] = st
                     finally:
-                        self.dec.free_nested(a)
-                finally:
-                    if conv is not None:
-                        self.dec.free(conv)
-            return out
+                        self.dec.free_structs(a)
+            return tree.build(root, columns, structs, rows, info)
         finally:
             self.dec.free(dev)
 
