@@ -790,6 +790,18 @@ int pqg_file_schema_node_kind(const pqg_file* f, int i);
 int pqo_decode_chunk(const pqg_chunk_job* job, pqg_chunk_result* res,
                      pqg_page_info* pages, int page_cap, int* n_pages);
 void pqo_free_result(pqg_chunk_result* res);
+/* The oracle's PageHeader.Read over buf[0, len): the status (PQG_OK or PQG_ERR_THRIFT), the bytes
+ * the reader consumed (also on an error: where it stopped) and every field it keeps, each
+ * page-header struct's on its own (a header may carry several). */
+typedef struct pqo_page_header {
+  int32_t type, uncompressed_size, compressed_size;
+  int32_t has_dph, has_dict, has_v2;
+  int32_t dph_num_values, dph_encoding, dph_def_encoding, dph_rep_encoding;
+  int32_t dict_num_values, dict_encoding;
+  int32_t v2_num_values, v2_num_nulls, v2_num_rows, v2_encoding, v2_def_len, v2_rep_len;
+  int32_t v2_is_compressed;
+} pqo_page_header;
+int pqo_read_page_header(const uint8_t* buf, int64_t len, int64_t* consumed, pqo_page_header* out);
 int pqo_unpack8_32(const uint8_t* data, int width, int32_t* out8);
 int pqo_unpack8_64(const uint8_t* data, int width, int64_t* out8);
 /* hybrid RLE/bit-pack: decode `count` values of `width` bits (levelDecoder.next) */

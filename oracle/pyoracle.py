@@ -25,6 +25,19 @@ class StoreRG(C.Structure):
                 ("chars", C.c_int64)]
 
 
+class PageHeader(C.Structure):
+    """pqo_page_header (include/pqgpu.h)."""
+    _fields_ = [(n, C.c_int32) for n in (
+        "type", "uncompressed_size", "compressed_size", "has_dph", "has_dict", "has_v2",
+        "dph_num_values", "dph_encoding", "dph_def_encoding", "dph_rep_encoding",
+        "dict_num_values", "dict_encoding",
+        "v2_num_values", "v2_num_nulls", "v2_num_rows", "v2_encoding", "v2_def_len", "v2_rep_len",
+        "v2_is_compressed")]
+
+    def fields(self):
+        return tuple(getattr(self, n) for n, _ in self._fields_)
+
+
 def lib():
     global _lib
     if _lib is None:
@@ -52,8 +65,17 @@ def lib():
         L.pqo_pack_levels.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
         L.pqo_go_roundupsize.argtypes = [C.c_int64]
         L.pqo_go_roundupsize.restype = C.c_int64
+        L.pqo_read_page_header.argtypes = [C.c_char_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(PageHeader)]
         _lib = L
     return _lib
+
+
+def read_page_header(buf: bytes):
+    """(status, bytes consumed, PageHeader) of the oracle's PageHeader.Read over `buf`."""
+    h = PageHeader()
+    n = C.c_int64(0)
+    rc = lib().pqo_read_page_header(bytes(buf), len(buf), C.byref(n), C.byref(h))
+    return rc, n.value, h
 
 
 def unpack8(data: bytes, width: int, bits: int = 32):

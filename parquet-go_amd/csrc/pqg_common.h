@@ -48,7 +48,9 @@ enum : int32_t {
 // Header fields of one page (thrift PageHeader subset, parquet.go:5794-5803).
 struct PageHdr {
   int32_t type, usize, csize;
-  int32_t num_values, encoding, def_enc, rep_enc;   // DataPageHeader / Dict / V2
+  int32_t num_values, encoding, def_enc, rep_enc;   // DataPageHeader
+  int32_t dict_num_values, dict_encoding;           // DictionaryPageHeader
+  int32_t v2_num_values, v2_encoding;               // DataPageHeaderV2 (a header may carry several structs)
   int32_t v2_def_len, v2_rep_len;
   int32_t has_dph, has_dict, has_v2;
   int32_t hlen;  // header bytes
@@ -381,6 +383,12 @@ constexpr int kPresentBigDict = 8;  // stage flag (kModePresentOff + 8): a page 
 constexpr int kScanTile = 16384;
 constexpr int kPrewalkPages = 4;  // K1: chunks of <= this many big pages are walked, not scanned
 constexpr int kCandPerTile = 64;
+// Limits of one lane's candidate parse (parse_candidate in pqg_scan.hip, where
+// each is explained; tools/thrift_model.cpp runs the parser under the same).
+constexpr int64_t kCandParseBytes = 1024;
+constexpr int kCandFrames = 4, kCandLast = 8;
+constexpr int kCandSteps = 40;
+constexpr int kCandWin = 10;  // granules: >= 144 bytes from any start
 
 // A page-header candidate: a position whose bytes parse as a PageHeader
 // (parsed by one lane, classified as if it were the chunk's first dictionary

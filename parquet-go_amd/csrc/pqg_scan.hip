@@ -58,8 +58,12 @@ __device__ __forceinline__ int classify_page(const JobDev& job, const PageHdr& h
                              PageDev& pg, int64_t* next, int64_t* comp) {
   *comp = 0;
   *next = payload;
+  // each page-header struct keeps its own fields (a header may carry several:
+  // the page's type says which one counts)
+  const int32_t h_nv = h.type == 2 ? h.dict_num_values : h.type == 3 ? h.v2_num_values : h.num_values;
+  const int32_t h_enc = h.type == 2 ? h.dict_encoding : h.type == 3 ? h.v2_encoding : h.type == 0 ? h.encoding : 0;
   pg.page_type = h.type;
-  pg.encoding = h.encoding;
+  pg.encoding = e == kOK ? h_enc : 0;  // a header that failed to parse has none
   pg.num_values = 0;
   pg.csize = h.csize;
   pg.usize = h.usize;
@@ -69,11 +73,11 @@ __device__ __forceinline__ int classify_page(const JobDev& job, const PageHdr& h
   pg.rep_enc = h.rep_enc;
   if (e != kOK) return e;
   if (h.type == 2) {  // DICTIONARY_PAGE (page_dict.go:30-64, chunk_reader.go:221-251)
-    pg.num_values = h.has_dict ? h.num_values : 0;
+    pg.num_values = h.has_dict ? h_nv : 0;
     if (dict_seen) e = kDICT_PAGE;
     else if (job.type == 0 || (job.type == 7 && job.type_length < 0)) e = kUNSUPPORTED;
-    else if (!h.has_dict || h.num_values < 0) e = kPAGE_HEADER;
-    else if (h.encoding != 0 && h.encoding != 2) e = kUNSUPPORTED;
+    else if (!h.has_dict || h_nv < 0) e = kPAGE_HEADER;
+    else if (h_enc != 0 && h_enc != 2) e = kUNSUPPORTED;
     else if (h.csize < 0 || h.usize < 0) e = kPAGE_HEADER;
     else if (job.data_len - payload < (int64_t)h.csize) e = kSIZE;
     else if (job.codec == 0) { if (h.csize != h.usize) e = kSIZE; }
@@ -83,13 +87,13 @@ __device__ __forceinline__ int classify_page(const JobDev& job, const PageHdr& h
     if (e == kOK && job.has_dict_off) *next = job.data_page_offset;
     if (e != kOK) *comp = 0;
   } else if (h.type == 0) {  // DATA_PAGE (page_v1.go:57-108)
-    pg.num_values = h.has_dph ? h.num_values : 0;
-    int enc = h.encoding == 2 ? 8 : h.encoding;
+    pg.num_values = h.has_dph ? h_nv : 0;
+    int enc = h_enc == 2 ? 8 : h_enc;
     pg.encoding = enc;
     if (!h.has_dph) e = kPAGE_HEADER;
     else if (job.max_rep > 0 && h.rep_enc != 3) e = kUNSUPPORTED;
     else if (job.max_def > 0 && h.def_enc != 3) e = kUNSUPPORTED;
-    else if (h.num_values < 0) e = kPAGE_HEADER;
+    else if (h_nv < 0) e = kPAGE_HEADER;
     else if (h.csize < 0 || h.usize < 0) e = kPAGE_HEADER;
     else if (job.data_len - payload < (int64_t)h.csize) e = kSIZE;
     else if (job.codec == 0 && h.csize != h.usize) e = kSIZE;
@@ -98,15 +102,15 @@ __device__ __forceinline__ int classify_page(const JobDev& job, const PageHdr& h
     if (e == kOK && job.codec != 0) *comp = ((int64_t)h.usize + 15) & ~(int64_t)15;
     *next = payload + h.csize;
   } else if (h.type == 3) {  // DATA_PAGE_V2 (page_v2.go:56-129)
-    pg.num_values = h.has_v2 ? h.num_values : 0;
-    int enc = h.encoding == 2 ? 8 : h.encoding;
+    pg.num_values = h.has_v2 ? h_nv : 0;
+    int enc = h_enc == 2 ? 8 : h_enc;
     pg.encoding = enc;
     int32_t levels = (int32_t)((uint32_t)h.v2_rep_len + (uint32_t)h.v2_def_len);
     int32_t cs = (int32_t)((uint32_t)h.csize - (uint32_t)levels);
     int32_t us = (int32_t)((uint32_t)h.usize - (uint32_t)levels);
     int64_t body = payload + (levels > 0 ? levels : 0);
     if (!h.has_v2) e = kPAGE_HEADER;
-    else if (h.num_values < 0 || h.v2_rep_len < 0 || h.v2_def_len < 0) e = kPAGE_HEADER;
+    else if (h_nv < 0 || h.v2_rep_len < 0 || h.v2_def_len < 0) e = kPAGE_HEADER;
     else if (!values_supported(job.type, job.type_length, enc)) e = kUNSUPPORTED;
     else if (levels > 0 && job.data_len - payload < (int64_t)levels) e = kEOF;
     else if (cs < 0 || us < 0) e = kPAGE_HEADER;
@@ -167,8 +171,8 @@ __device__ __forceinline__ void init_job_results(JobDev& job) {
 // end, at most kCandParseBytes past the candidate): a header that needs more
 // is left to the serial walk (`hit`), so a garbage candidate cannot run away
 // through the chunk (e.g. a thrift list header claiming 2^31 elements).
-// Bytes past the chunk read as -1 (EOF) without `hit`.
-constexpr int64_t kCandParseBytes = 1024;
+// Bytes past the chunk read as -1 (EOF) without `hit`.  (The limits are in
+// pqg_common.h: the host model of this parse shares them.)
 struct CandSrc {
   const PQG_L uint8_t* win;  // bytes [wlo, limit) of the chunk
   int64_t wlo, limit, n;
@@ -187,24 +191,23 @@ __device__ __forceinline__ bool has_byte_15(uint32_t x) {
   return ((y - 0x01010101u) & ~y & 0x80808080u) != 0;
 }
 
-constexpr int kCandFrames = 4, kCandLast = 8;
-// Loop steps of one candidate parse (fields + skipped container elements):
+// kCandFrames, kCandLast: the parse's skip-frame and lastField stacks.
+// kCandSteps: loop steps of one candidate parse (fields + skipped container elements):
 // the headers of parquet writers take at most ~25 (PageHeader, its page
 // header struct and a Statistics struct); garbage that runs longer is
 // kCOMPLEX (the serial walk reads it if a page link ever lands on it).  A
 // lane's steps set its wave's time: without the bound one garbage candidate
 // of ~80 one-byte fields held its wave ~0.2 ms.
-constexpr int kCandSteps = 40;
 
 // One lane parses and classifies the candidate at position p (kept out of
 // line: the scan loop around it must stay small).
-// The candidate's first bytes are prefetched into the lane's LDS window with
+// The candidate's first bytes are prefetched into the lane's LDS window
+// (kCandWin granules) with
 // independent 16-byte loads, and the parse is confined to them: a header that
 // does not end inside the window is kCOMPLEX (its chunk takes the serial walk
 // only if a page link lands on it).  Without the bound, the slowest candidate
 // — garbage that passes the pre-check and reads on through the chunk one
 // dependent granule load at a time — set the kernel's time.
-constexpr int kCandWin = 10;  // granules: >= 144 bytes from any start
 __device__ __forceinline__ void parse_candidate(const JobDev& job, int64_t p, SkipFrame* frames, int16_t* lasts,
                                              PQG_L uint8_t* win, Cand* out) {
   Compact<CandSrc> c;
@@ -262,7 +265,7 @@ __device__ __forceinline__ void parse_candidate(const JobDev& job, int64_t p, Sk
   Cand cd;
   cd.pos = p;
   cd.next = next;
-  cd.payload = c.pos;
+  cd.payload = c.pos < job.data_len ? c.pos : job.data_len;  // a failed read stops at the chunk's end
   cd.comp = comp;
   cd.type = pg.page_type;
   cd.encoding = pg.encoding;
@@ -769,7 +772,7 @@ struct ScanShared {
 // against it byte for byte, 64 pages per round, one per lane, with one round
 // of loads: identical header bytes read identically (the same fields, shifted
 // positions), so the page's record is page 0's with its offsets.  The chunk's
-// last page (fewer rows) is parsed and must end at or past the chunk's end.
+// last page, when shorter (fewer rows), is parsed and must end at or past the chunk's end.
 // Any other difference returns false: the candidate scan then settles the
 // chunk and overwrites every page record written here.  The pages before
 // spos (a dictionary page, big pages) are the serial walk's.
@@ -832,7 +835,9 @@ __device__ bool stride_walk(JobDev& job, int j, PageDev* pages, int64_t spos, in
     Cand ck = c0;
     bool ok = same;
     if (live && !same) {
-      if (lastp) {  // the short last page: parsed, and it must end the chunk
+      // the short last page: parsed, and it must end the chunk (a last page of
+      // full length whose header differs is a difference like any other)
+      if (lastp && tcs - q < slen) {
         parse_candidate(job, q, sh.cf[lane], sh.cl[lane], lds_ptr(sh.cw[lane]), &ck);
         ok = ck.status == kOK && (ck.type == 0 || ck.type == 3) && ck.next >= tcs;
       }
@@ -1011,7 +1016,7 @@ __global__ void __launch_bounds__(64) k_scan_pages(JobDev* jobs, PageDev* pages,
     int e = c.read_page_header(&h);
     win = c.src.w;
     PageDev pg;
-    init_page(pg, j, pos, c.pos);
+    init_page(pg, j, pos, c.pos < job.data_len ? c.pos : job.data_len);  // a failed read stops at the chunk's end
     pg.slot_offset = slots;
     int64_t next, comp;
     e = classify_page(job, h, e, c.pos, dict_seen, pg, &next, &comp);

@@ -346,6 +346,7 @@ struct Compact {
     int64_t start = pos;
     h->type = h->usize = h->csize = 0;
     h->num_values = h->encoding = h->def_enc = h->rep_enc = 0;
+    h->dict_num_values = h->dict_encoding = h->v2_num_values = h->v2_encoding = 0;
     h->v2_def_len = h->v2_rep_len = 0;
     h->has_dph = h->has_dict = h->has_v2 = 0;
     // known-struct stack (PageHeader -> DPH / V2 -> Statistics: depth <= 3),
@@ -398,7 +399,7 @@ struct Compact {
         if (id >= 1 && id <= 4 && t == T_I32) { act = A_I32; slot = 3 + id; bit = 1u << (id - 1); }
         else if (id == 5 && t == T_STRUCT) { act = A_STRUCT; child = S_STAT; }
       } else if (sc == S_DICT) {
-        if (id >= 1 && id <= 2 && t == T_I32) { act = A_I32; slot = 3 + id; bit = 1u << (id - 1); }
+        if (id >= 1 && id <= 2 && t == T_I32) { act = A_I32; slot = 14 + id; bit = 1u << (id - 1); }
         else if (id == 3 && t == T_BOOL) act = A_BOOL;
       } else if (sc == S_V2) {
         if (id >= 1 && id <= 6 && t == T_I32) { act = A_I32; slot = 8 + id; bit = 1u << (id - 1); }
@@ -424,16 +425,20 @@ struct Compact {
         int32_t v = 0;
         e = i32(&v);
         seen |= bit;
-        if (!e) switch (slot) {  // a failed read leaves the field as it was  // 0-3 PageHeader, 4-7 DPH, 5-6 dictionary, 9-14 V2
+        if (!e) switch (slot) {  // a failed read leaves the field as it was  // 0-3 PageHeader, 4-7 DPH, 9-14 V2, 15-16 dictionary
           case 0: h->type = v; break;
           case 1: h->usize = v; break;
           case 2: h->csize = v; break;
-          case 4: case 9: h->num_values = v; break;
-          case 5: case 12: h->encoding = v; break;
+          case 4: h->num_values = v; break;
+          case 5: h->encoding = v; break;
           case 6: h->def_enc = v; break;
           case 7: h->rep_enc = v; break;
+          case 9: h->v2_num_values = v; break;
+          case 12: h->v2_encoding = v; break;
           case 13: h->v2_def_len = v; break;
           case 14: h->v2_rep_len = v; break;
+          case 15: h->dict_num_values = v; break;
+          case 16: h->dict_encoding = v; break;
           default: break;  // crc, num_nulls, num_rows
         }
       } else if (act == A_BOOL) {

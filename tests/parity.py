@@ -66,17 +66,25 @@ def compare_file(data, dec, rgs=None, cols=None):
         dec.free(dev)
 
 
-def compare_chunk_bytes(chunk, dec, **kw):
-    """Hand-built chunk bytes (see pqtest_util.chunk_job) through both paths."""
+def compare_chunk_bytes(chunk, dec, offset=0, exp=None, page_cap=None, **kw):
+    """Hand-built chunk bytes (see pqtest_util.chunk_job) through both paths; on the device the
+    chunk starts `offset` bytes into the uploaded buffer.  `exp`: the oracle's result of an earlier
+    call for the same chunk and job; `page_cap`: at most so many page records are fetched (the
+    default allocates room for 2^20 on either side)."""
     import pqtest_util as U
     keep = []
     job, buf = U.chunk_job(chunk, keep=keep, **kw)
-    exp = O.decode_chunk(job)
-    dev = dec.upload(buf)
+    if exp is None:
+        exp = O.decode_chunk(job) if page_cap is None else O.decode_chunk(job, page_cap)
+    dev = dec.upload(np.concatenate([np.zeros(offset, np.uint8), buf]) if offset else buf)
     try:
-        job.data = dev
+        job.data = dev + offset
         r = dec.decode_jobs([job])[0]
-        got = dec.download(r, 0)
+        if page_cap is None:
+            got = dec.download(r, 0)
+        else:
+            got = dec.download(r)
+            got.pages = dec.pages(0, page_cap)
         compare_chunk(exp, got, "chunk")
         return exp, got
     finally:
