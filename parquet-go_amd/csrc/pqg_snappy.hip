@@ -44,11 +44,15 @@ int prof_read_snappy(unsigned long long* out) {
 //    one per lane, a copy one byte per lane — and the following tags are
 //    taken one at a time too (the next header read ahead of the current
 //    tag's bytes) until a streak of short tags sends the wave back to 1-3.
-// The output history is a 64 KiB LDS ring: every copy-1/copy-2 offset
-// (< 64 KiB) reads it; older bytes (copy-4) come from the flushed output
-// through L2.  The ring leaves for HBM in 16-byte granules with each window
-// refill (whose load wait then also covers the stores) or every 16 KiB.  A
-// literal longer than the window goes from HBM in 4 KiB pieces.
+// The output history is an LDS ring of kRing bytes (4 KiB by default): it
+// holds the output [ring_lo, d), ring_lo = roundup16(d) - kRing.  A copy whose
+// source starts below ring_lo, whatever its form (copy-2 offsets reach
+// 64 KiB, copy-4 further), reads the flushed output through L2 instead.  The
+// ring leaves for HBM in 16-byte granules with each window refill (whose load
+// wait then also covers the stores) or every kSnFlush bytes.  A literal too
+// long for a batch goes from HBM in kLongPiece pieces.
+// (tests/snappy_build.py restates these constants and the path each tag
+// takes; profiles/snappy_edges.md records the paths of the directed cases.)
 // ============================================================================
 constexpr int kPos = 128;         // tag positions parsed per window (2 per lane)
 #ifndef PQG_SNAPPY_DENSE
@@ -534,9 +538,9 @@ struct SnapBlock {
       const uint8_t b = lds_ptr(sh->ring)[(uint32_t)h & (kRing - 1)];
       if (lane < len) lds_ptr(sh->ring)[(uint32_t)(d + lane) & (kRing - 1)] = b;
     } else {
-      // older than the ring (copy-4): the flushed output through L2, once the
-      // flush stores have landed and this CU's L1 holds no stale line
-      // (off > kRing - 16 > len: no overlap)
+      // older than the ring (any copy-2 or copy-4 offset above kRing - 16 can
+      // be): the flushed output through L2, once the flush stores have landed
+      // and this CU's L1 holds no stale line (off > kRing - 16 > len: no overlap)
       flush(d & ~15);
       __builtin_amdgcn_s_waitcnt(0);  // this wave's flush stores have reached L2
       // every lane loads (h < d for all 64: off > 64), so that no load is

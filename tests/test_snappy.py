@@ -14,73 +14,7 @@ import pytest
 
 from oracle import pyoracle as O
 from pqgpu import abi
-
-
-def lit(b):
-    n = len(b) - 1
-    if n < 60:
-        h = bytes([n << 2])
-    elif n < 1 << 8:
-        h = bytes([60 << 2, n])
-    elif n < 1 << 16:
-        h = bytes([61 << 2]) + n.to_bytes(2, "little")
-    elif n < 1 << 24:
-        h = bytes([62 << 2]) + n.to_bytes(3, "little")
-    else:
-        h = bytes([63 << 2]) + n.to_bytes(4, "little")
-    return h + bytes(b)
-
-
-def copy(off, ln, form):
-    if form == 1:
-        assert 4 <= ln <= 11 and off < 2048
-        return bytes([1 | (ln - 4) << 2 | (off >> 8) << 5, off & 255])
-    if form == 2:
-        assert 1 <= ln <= 64 and off < 65536
-        return bytes([2 | (ln - 1) << 2, off & 255, off >> 8])
-    assert 1 <= ln <= 64
-    return bytes([3 | (ln - 1) << 2]) + off.to_bytes(4, "little")
-
-
-def uvarint(n):
-    o = bytearray()
-    while n >= 0x80:
-        o.append(n & 0x7F | 0x80)
-        n >>= 7
-    o.append(n)
-    return bytes(o)
-
-
-def stream(rng, target, far_frac=0.2, lit_max=40, long_lit=0.01):
-    """Random tag stream of about `target` output bytes -> (compressed, plaintext)."""
-    out = bytearray()
-    tags = []
-    while len(out) < target:
-        r = rng.random()
-        if not out or r < 0.3:
-            n = int(rng.integers(1, lit_max + 1)) if rng.random() > long_lit else int(rng.integers(60, 5000))
-            b = rng.integers(0, 256, n, dtype=np.uint8).tobytes()
-            tags.append(lit(b))
-            out += b
-            continue
-        d = len(out)
-        if r < 0.45:  # overlapping run-length copy
-            off = int(rng.integers(1, min(d, 8) + 1))
-        elif r < 0.45 + far_frac and d > 17000:
-            off = int(rng.integers(16400, min(d, 65535) + 1))
-        else:
-            off = int(rng.integers(1, min(d, 3000) + 1))
-        ln = int(rng.integers(1, 65))
-        if off < 2048 and 4 <= ln <= 11 and rng.random() < 0.5:
-            form = 1
-        elif rng.random() < 0.1:
-            form = 4
-        else:
-            form = 2
-        tags.append(copy(off, ln, form))
-        for _ in range(ln):
-            out.append(out[-off])
-    return uvarint(len(out)) + b"".join(tags), bytes(out)
+from snappy_build import copy, lit, stream, uvarint
 
 
 def cases():
@@ -128,24 +62,21 @@ def test_snappy_tag_forms(dec):
         assert rc == 0 and got == exp
 
 
-@pytest.mark.gpu
-def test_snappy_corruptions(dec):
-    """Byte flips, truncations and bad offsets: the GPU and the oracle agree on
-    success/failure and, on success, on every byte."""
+BAD = [uvarint(10) + copy(1, 4, 1),                      # copy before any output
+       uvarint(10) + lit(b"abc") + copy(4, 4, 1),        # offset > d
+       uvarint(5) + lit(b"abc") + copy(1, 5, 2),         # past the declared length
+       uvarint(10) + lit(b"abc"),                        # short output
+       uvarint(3) + bytes([61 << 2, 2]),                 # truncated literal header
+       uvarint(3) + bytes([8]) + b"ab",                  # literal past the block end
+       uvarint(4) + lit(b"ab") + copy(0, 2, 2),          # zero offset
+       uvarint(2) + lit(b"ab") + bytes([3])]             # truncated copy-4
+
+
+def mutants():
+    """60 seeded mutations (a changed byte, a truncation, an inserted byte) of each of two random streams."""
     rng = np.random.default_rng(12)
     base = [stream(rng, 20_000)[0], stream(rng, 3000, lit_max=5)[0]]
-    bad = [uvarint(10) + copy(1, 4, 1),                      # copy before any output
-           uvarint(10) + lit(b"abc") + copy(4, 4, 1),        # offset > d
-           uvarint(5) + lit(b"abc") + copy(1, 5, 2),         # past the declared length
-           uvarint(10) + lit(b"abc"),                        # short output
-           uvarint(3) + bytes([61 << 2, 2]),                 # truncated literal header
-           uvarint(3) + bytes([8]) + b"ab",                  # literal past the block end
-           uvarint(4) + lit(b"ab") + copy(0, 2, 2),          # zero offset
-           uvarint(2) + lit(b"ab") + bytes([3])]             # truncated copy-4
-    n = 0
-    for s in bad:
-        rc, _ = _gpu(dec, s)
-        assert rc != 0 and O.snappy_decode(s)[0] != 0, s
+    out = []
     for s in base:
         for _ in range(60):
             m = bytearray(s)
@@ -158,10 +89,35 @@ def test_snappy_corruptions(dec):
             else:
                 i = int(rng.integers(3, len(m)))
                 m[i:i] = bytes([int(rng.integers(0, 256))])
-            rc, got = _gpu(dec, bytes(m))
-            rc_o, exp = O.snappy_decode(bytes(m))
-            assert (rc == 0) == (rc_o == 0), (k, rc, rc_o)
-            if rc == 0:
-                assert got == exp
-                n += 1
-    assert n >= 0
+            out.append((k, bytes(m)))
+    return out
+
+
+def oracle_decodes():
+    """How many of the mutants the oracle alone decodes."""
+    return sum(1 for _, m in mutants() if O.snappy_decode(m)[0] == 0)
+
+
+def test_mutants_have_both_verdicts():
+    n = len(mutants())
+    assert n // 20 <= oracle_decodes() <= n - n // 20
+
+
+@pytest.mark.gpu
+def test_snappy_corruptions(dec):
+    """Byte flips, truncations and bad offsets: the GPU and the oracle agree on
+    success/failure (on the hand-written ones, on the status) and, on success,
+    on every byte."""
+    n = 0
+    for s in BAD:
+        rc, _ = _gpu(dec, s)
+        rc_o = O.snappy_decode(s)[0]
+        assert rc != 0 and rc == rc_o, (s, rc, rc_o)
+    for k, m in mutants():
+        rc, got = _gpu(dec, m)
+        rc_o, exp = O.snappy_decode(m)
+        assert (rc == 0) == (rc_o == 0), (k, rc, rc_o)
+        if rc == 0:
+            assert got == exp
+            n += 1
+    assert n == oracle_decodes()

@@ -7,6 +7,7 @@ corrupt one go back to the one-wave decode of the whole block, which the page
 flag PQG_PAGE_FLAG_SNAPPY_SERIAL records.  Every case is GPU vs the oracle
 (decode_other.go:14-101 restated), bit for bit, on both paths."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
@@ -119,7 +120,7 @@ def test_split_mixed_literals_and_runs(dec):
 def _blocks_stream(rng, nblocks, tail):
     """A snappy stream of `nblocks` independent 64 KiB blocks plus a `tail`-byte
     block, built tag by tag (copies never reach into an earlier block)."""
-    import test_snappy as S
+    import snappy_build as S
     out = bytearray()
     tags = []
     for b in range(nblocks + 1):
@@ -144,15 +145,43 @@ def _blocks_stream(rng, nblocks, tail):
     return S.uvarint(len(out)) + b"".join(tags), bytes(out)
 
 
+SPLIT_SHAPES = ((1, 0), (3, 17), (5, 65535), (2, 1))  # (64 KiB blocks, bytes of the last block)
+
+
+@functools.lru_cache(maxsize=None)
+def split_streams():
+    """[(stream, plaintext, 25 single-byte mutants)] per shape, from one seeded generator."""
+    rng = np.random.default_rng(21)
+    out = []
+    for nb, tail in SPLIT_SHAPES:
+        src, plain = _blocks_stream(rng, nb, tail)
+        ms = []
+        for _ in range(25):
+            m = bytearray(src)
+            i = int(rng.integers(4, len(m)))
+            m[i] = int(rng.integers(0, 256))
+            ms.append(bytes(m))
+        out.append((src, plain, ms))
+    return out
+
+
+def oracle_decodes():
+    """How many of the mutants the oracle alone decodes."""
+    return sum(1 for _, _, ms in split_streams() for m in ms if O.snappy_decode(m)[0] == 0)
+
+
+def test_split_mutants_have_both_verdicts():
+    n = sum(len(ms) for _, _, ms in split_streams())
+    assert oracle_decodes() >= n // 20
+
+
 @pytest.mark.gpu
 def test_block_decompress_split_streams(dec):
     """pqg_block_decompress runs the same split stage on its one block: streams
     of independent 64 KiB blocks (tag forms, long literals, run-length copies,
     a block ending exactly on a boundary) and their corruptions."""
-    rng = np.random.default_rng(21)
     n = 0
-    for nb, tail in ((1, 0), (3, 17), (5, 65535), (2, 1)):
-        src, plain = _blocks_stream(rng, nb, tail)
+    for src, plain, ms in split_streams():
         rc_o, exp = O.snappy_decode(src)
         assert rc_o == 0 and exp == plain
         dst = np.zeros(len(plain) + 64, np.uint8)
@@ -160,18 +189,14 @@ def test_block_decompress_split_streams(dec):
         rc = dec.L.pqg_block_decompress(dec.ctx, abi.CODEC_SNAPPY, src, len(src), dst.ctypes.data, len(dst),
                                         C.byref(got))
         assert rc == 0 and dst[:got.value].tobytes() == plain
-        for _ in range(25):  # corruptions: same outcome class as the oracle
-            m = bytearray(src)
-            i = int(rng.integers(4, len(m)))
-            m[i] = int(rng.integers(0, 256))
-            rc_o, exp = O.snappy_decode(bytes(m))
+        for m in ms:  # corruptions: the oracle's status
+            rc_o, exp = O.snappy_decode(m)
             dst[:] = 0
-            rc = dec.L.pqg_block_decompress(dec.ctx, abi.CODEC_SNAPPY, bytes(m), len(m), dst.ctypes.data, len(dst),
-                                            C.byref(got))
+            rc = dec.L.pqg_block_decompress(dec.ctx, abi.CODEC_SNAPPY, m, len(m), dst.ctypes.data, len(dst), C.byref(got))
             if rc_o == abi.STATUS_CODES["SIZE"]:
                 continue  # a varint flip: the buffer is sized from it (CAPACITY) — class checked elsewhere
             assert rc == rc_o, (rc, rc_o)
             if rc == 0:
                 assert dst[:got.value].tobytes() == exp
                 n += 1
-    assert n >= 0
+    assert n == oracle_decodes()
