@@ -23,7 +23,13 @@
 // flow); tables are built by lane 0, Huffman streams are decoded one per lane.
 // What is accepted and rejected follows libzstd's ZSTD_decompress (where it is
 // laxer than the RFC, so is this: no block-size limit on raw / RLE blocks, no
-// window check on offsets, Huffman codes of 12 bits).
+// window check on offsets, Huffman codes of 12 bits).  One laxity is this
+// decoder's own: a compressed block may regenerate more than the block
+// maximum; output stays bounded by `cap`.  (The RFC forbids such a block;
+// libzstd takes it up to the block maximum + 67 bytes, an accident of where
+// it keeps the block's literals.  No writer emits one.  A buffer sized by
+// decoded_bound below, as pqg_block_decompress sizes its own, holds the block
+// maximum per compressed block: there the bytes past it are an error.)
 #pragma once
 #include <stdint.h>
 
