@@ -114,7 +114,9 @@ enum {
   PQG_ERR_INVALID_ARG = -21,
   PQG_ERR_HIP = -22,
   PQG_ERR_METADATA = -23,     /* footer / FileMetaData problems                      */
-  PQG_ERR_NOT_BUILT = -24
+  PQG_ERR_NOT_BUILT = -24,
+  PQG_ERR_INDEX = -25         /* located decode: a listed page whose header and body do */
+                              /* not end at offset + size (a read-phase error)           */
 };
 
 /* page_info.flags */
@@ -266,6 +268,79 @@ int pqg_sync(pqg_ctx* ctx, pqg_chunk_result* results, int n_jobs);
 /* Convenience: async + sync. */
 int pqg_decode_chunks(pqg_ctx* ctx, const pqg_chunk_job* jobs, int n_jobs,
                       pqg_chunk_result* results);
+
+/* ---- located decode: the pages of a chunk given by the caller (an OffsetIndex) ---------
+ *
+ * A job decoded with a list of page locations is not scanned for page headers: each listed
+ * page's header is parsed where the list says it is.  The list may be any subset of the
+ * chunk's pages, in ascending order.  Its meaning is that of a scanned decode: the located
+ * decode of job J with locations L gives what pqg_decode_chunks gives for the job J' whose
+ * `data` is the bytes of L's pages back to back, with total_compressed_size = the sum of the
+ * sizes, has_dict_page_offset = 0 and everything else as in J -- levels, values, offsets,
+ * num_slots, num_values, status, error_page and every page-table field but header_offset and
+ * payload_offset, which stay relative to J.data.  So the dictionary page, when wanted, is
+ * simply the first location; a list without it, of it alone, or of every other data page is
+ * legal and means what J' means.  One addition: a listed page whose own read phase is fine
+ * but whose header and body do not end at offset + size fails its read phase with
+ * PQG_ERR_INDEX; it ranks like any read-phase error (the first failing page in list order
+ * wins, the pages before it are reported, no decoder reads it).
+ *
+ * pages[i].n == 0: job i is scanned as by pqg_decode_chunks; one batch may mix both kinds.
+ * Of a located job, total_compressed_size, data_page_offset and has_dict_page_offset are
+ * capacity hints only.  PQG_ERR_INVALID_ARG, with nothing enqueued: n < 0, an offset < 0, a
+ * size <= 0, offset + size > data_len, offsets that do not ascend or ranges that overlap.
+ * PQG_COL_KEEP_DICT, pqg_set_verify_crc, pqg_get_pages, pqg_get_dictionary,
+ * pqg_get_page_crcs and pqg_last_timings work as after a scanned decode; pqg_debug_job
+ * reports out[0] = 3 and 0 candidates for a located job.  The lists are copied at submit. */
+typedef struct pqg_page_loc {
+  int64_t offset;      /* of the PageHeader; for the decode: relative to job.data */
+  int32_t size;        /* header + body, PageLocation.compressed_page_size */
+  int32_t reserved;
+  int64_t first_row;   /* PageLocation.first_row_index; not used by the decode */
+} pqg_page_loc;
+typedef struct pqg_chunk_pages {
+  const pqg_page_loc* locs; /* HOST */
+  int32_t n;
+  int32_t reserved;
+} pqg_chunk_pages;
+int pqg_decode_chunks_located_async(pqg_ctx* ctx, const pqg_chunk_job* jobs, const pqg_chunk_pages* pages, int n_jobs);
+/* Convenience: async + pqg_sync. */
+int pqg_decode_chunks_located(pqg_ctx* ctx, const pqg_chunk_job* jobs, const pqg_chunk_pages* pages, int n_jobs,
+                              pqg_chunk_result* results);
+
+/* More of the located contract.  A `pages[i]` with n > 0 and a NULL `locs` is PQG_ERR_INVALID_ARG, and so
+ * is a batch that lists more than INT32_MAX / 2 pages in all.  A listed page's header is read within
+ * [offset, offset + size), but its body is checked against job.data_len, as a scanned page's is: a page
+ * listed too short reports PQG_ERR_INDEX where the bytes after it are resident, and PQG_ERR_SIZE where
+ * the list's end is the end of the data (the last page of a packed upload). */
+
+/* ---- the page index (host parsers; parquet.thrift OffsetIndex / ColumnIndex) --------------
+ * pqg_file_chunk_index: where a chunk's indexes lie in the file (ColumnChunk fields 4-7); a length of 0
+ * means that index is absent.  The parsers take the index's bytes as the file holds them and trust
+ * nothing: PQG_ERR_METADATA for a truncated or malformed struct, bytes left over, parallel lists of
+ * different lengths, a size <= 0, negative or descending offsets or first rows, overlapping pages, a
+ * negative null count or an unknown boundary order.
+ * pqg_parse_offset_index returns the number of locations (the first `cap` are written; offsets are
+ * absolute file offsets as stored).  A parsed ColumnIndex is a handle: pqg_column_index_page gives page
+ * `page`'s bounds and null count as a pqg_chunk_stats: pointers owned by the handle, min / max NULL for a
+ * null page, null_count -1 when the index has none; and whether it is a null page.
+ * pqg_column_index_boundary_order is 0 unordered, 1 ascending, 2 descending. */
+typedef struct pqg_index_ranges {
+  int64_t offset_index_offset;
+  int64_t column_index_offset;
+  int32_t offset_index_length;
+  int32_t column_index_length;
+} pqg_index_ranges;
+typedef struct pqg_column_index pqg_column_index;
+struct pqg_file;
+struct pqg_chunk_stats;
+int pqg_file_chunk_index(const struct pqg_file* f, int row_group, int col, pqg_index_ranges* out);
+int pqg_parse_offset_index(const uint8_t* buf, int64_t len, pqg_page_loc* out, int cap);
+int pqg_column_index_parse(const uint8_t* buf, int64_t len, pqg_column_index** out);
+int pqg_column_index_pages(const pqg_column_index* ci);
+int pqg_column_index_page(const pqg_column_index* ci, int page, struct pqg_chunk_stats* out, int32_t* null_page);
+int pqg_column_index_boundary_order(const pqg_column_index* ci);
+void pqg_column_index_free(pqg_column_index* ci);
 
 /* ---- page-level and codec-level entries ------------------------------------ */
 
@@ -657,6 +732,15 @@ typedef struct pqg_select_args {
   int64_t bytes_out;           /* out: value bytes (chars for byte arrays)               */
 } pqg_select_args;
 int pqg_select(pqg_ctx* ctx, pqg_select_args* args);
+
+/* Row ranges into a row bitmap of pqg_filter's layout (LSB first, 4 * ceil(num_rows / 32) bytes at
+ * `bitmap`, a 4-byte aligned DEVICE pointer): bit r is set exactly when one of the n ranges
+ * [lo, hi) (`ranges`: n pairs of int64 on the HOST) holds r.  Whole dwords are written; the bits at
+ * and past num_rows are zero.  The ranges must ascend and be disjoint, with
+ * 0 <= lo <= hi <= num_rows (empty ranges are allowed), else PQG_ERR_INVALID_ARG with nothing
+ * written.  With pqg_select it trims a decoded column to a set of row ranges.  Synchronous; its
+ * device time is what pqg_last_filter_ms reports next. */
+int pqg_range_bitmap(pqg_ctx* ctx, const int64_t* ranges, int n, int64_t num_rows, uint8_t* bitmap);
 
 /* Device time (ms) of the kernels of the last pqg_filter / pqg_select call (an event
  * pair on the ctx stream; the literal upload and the count read-back excluded). */

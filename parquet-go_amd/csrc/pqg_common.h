@@ -42,6 +42,7 @@ enum : int32_t {
   kCRC = -18,        // PageHeader.crc does not match the page's bytes (k_crc_fin; only with verification on)
   kNOT_DICT = -19,   // keep-dictionary job (JobDev.keep_dict): a data page of another encoding than RLE_DICTIONARY
   kCAPACITY = -20,
+  kINDEX = -25,      // located decode: a listed page whose header does not end at offset + size (k_scan_located)
   kCOMPLEX = -30,   // internal: header needs the serial walk (deep thrift nesting)
 };
 
@@ -202,6 +203,7 @@ struct JobDev {
   int32_t n_tiles;         // ceil(min(tcs, data_len) / kScanTile)
   int32_t scan_fallback;   // 1: the serial walk (k_scan_pages) decodes this job's page list;
                            // 2: walked before the candidate scan (a few big pages)
+                           // 3: a located job (set by the host): its pages are listed, nothing is scanned
   int32_t n_cands;         // header candidates found in the job's bytes
   int32_t n_ok;            // candidates whose read phase succeeds
   int32_t brk;             // first ok-rank whose successor is not the next ok candidate
@@ -227,6 +229,20 @@ struct JobDev {
   const uint8_t* dict_chars;        // k_dict_export: the chars back to back (null: not exported)
   const int64_t* dict_aoffs;        // k_dict_export: count + 1 offsets into them
   int64_t dict_chars_len;           // k_dict_export: bytes of dict_chars (dict_aoffs[count])
+  // ---- located jobs (pqg_decode_chunks_located; k_scan_located, k_chain_located): the job's entries
+  // [loc_base, loc_base + n_locs) of the batch's location table.  n_locs > 0: scan_fallback is 3 (host),
+  // n_tiles 0, and brk / first_dict / second_dict count list positions, brk the first failing one
+  int64_t loc_base;
+  int32_t n_locs;
+  int32_t loc_pad;
+};
+
+// One entry of the batch's location table (located jobs): a page of job `job` at [offset, offset + size)
+// of the job's data, in list order.
+struct LocDev {
+  int64_t offset;
+  int32_t size;
+  int32_t job;
 };
 
 // The per-chunk bookkeeping kernels (k_page_chain, k_page_list, k_nn_scan,

@@ -153,6 +153,14 @@ struct pqg_ctx {
   // scan settles any chunk, so a stale entry never changes a result)
   std::map<pqg::JobKey, bool> many_pages;
   pqg::BatchTraits batch;               // the in-flight batch (pqg_decode_chunks_async)
+  // located jobs of the in-flight batch (pqg_decode_chunks_located_async): the batch's location table,
+  // uploaded once at submit, and each job's entries of it (n_locs 0: the job is scanned).  Such a job
+  // neither reads nor feeds `learned` / `many_pages`: their key does not tell a located job from the
+  // scanned one of the same chunk, or from another subset of its pages.
+  std::vector<pqg::LocDev> h_locs;
+  std::vector<int64_t> loc_base;
+  std::vector<int32_t> n_locs;
+  DevBuf locs;
   int launches = 0;                     // pipeline launches of the last decode
   int n_jobs = 0;
   int64_t list_cap = 0;

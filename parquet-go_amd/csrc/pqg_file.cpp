@@ -14,6 +14,7 @@
 
 #include "../../include/pqgpu.h"
 #include "pqg_thrift.h"
+#include "pqg_page_index.h"  // defines pqg_parse_offset_index and pqg_column_index_*
 
 using namespace pqg;
 
@@ -45,6 +46,9 @@ struct ChunkM {
   bool has_nulls = false, has_min = false, has_max = false;
   int64_t null_count = 0;
   std::string min_value, max_value;
+  // ColumnChunk fields 4-7: where the chunk's OffsetIndex / ColumnIndex lie in the file (length 0: none)
+  int64_t oi_off = 0, ci_off = 0;
+  int32_t oi_len = 0, ci_len = 0;
 };
 
 struct Leaf {
@@ -299,6 +303,8 @@ struct Parser {
         m->has_meta = true;
         return meta(m) ? 1 : -1;
       }
+      if ((id == 4 || id == 6) && t == T_I64) return c.i64(id == 4 ? &m->oi_off : &m->ci_off) ? -1 : 1;
+      if ((id == 5 || id == 7) && t == T_I32) return c.i32(id == 5 ? &m->oi_len : &m->ci_len) ? -1 : 1;
       return 0;
     });
   }
@@ -582,6 +588,25 @@ int pqg_file_chunk_stats(const pqg_file* f, int rg, int col, pqg_chunk_stats* ou
     out->max_len = (int32_t)m.max_value.size();
   }
   if (m.has_nulls) out->null_count = m.null_count;
+  return PQG_OK;
+}
+
+// ColumnChunk.offset_index_* / column_index_*: an index with a negative offset or length is reported absent.
+int pqg_file_chunk_index(const pqg_file* f, int rg, int col, pqg_index_ranges* out) {
+  if (!f || !out || rg < 0 || rg >= (int)f->rgs.size() || col < 0 || col >= (int)f->leaves.size())
+    return PQG_ERR_INVALID_ARG;
+  memset(out, 0, sizeof(*out));
+  const std::vector<ChunkM>& cols = f->rgs[(size_t)rg];
+  if ((int)cols.size() <= col) return PQG_ERR_METADATA;
+  const ChunkM& m = cols[(size_t)col];
+  if (m.oi_off > 0 && m.oi_len > 0) {
+    out->offset_index_offset = m.oi_off;
+    out->offset_index_length = m.oi_len;
+  }
+  if (m.ci_off > 0 && m.ci_len > 0) {
+    out->column_index_offset = m.ci_off;
+    out->column_index_length = m.ci_len;
+  }
   return PQG_OK;
 }
 

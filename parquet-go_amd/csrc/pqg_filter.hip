@@ -297,4 +297,37 @@ int select_launch(hipStream_t s, const Sel& a, int64_t* seg, int64_t* tot) {
   return hipGetLastError() == hipSuccess ? PQG_OK : PQG_ERR_HIP;
 }
 
+// ---- row ranges -> row bitmap (pqg_range_bitmap) ---------------------------------
+// One lane per bitmap dword (rows [32 d, 32 d + 32)): a binary search over the ascending, disjoint
+// ranges finds the first one that ends past the dword's first row, and the ranges from there on that
+// start before its end set their bits.  Every dword is written whole, so bits at and past num_rows
+// (no range holds them) are zero.
+__global__ void __launch_bounds__(256) k_range_bitmap(const int64_t* ranges, int n, int64_t ndw, uint32_t* bitmap) {
+  const int64_t d = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (d >= ndw) return;
+  const PQG_G int64_t* r = gconst(ranges);
+  const int64_t r0 = d * 32, r1 = r0 + 32;
+  int lo = 0, hi = n;  // first range with hi > r0
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (r[2 * mid + 1] > r0) hi = mid; else lo = mid + 1;
+  }
+  uint32_t bits = 0;
+  for (int k = lo; k < n; k++) {
+    const int64_t a = r[2 * k], b = r[2 * k + 1];
+    if (a >= r1) break;
+    const int x = (int)((a > r0 ? a : r0) - r0), y = (int)((b < r1 ? b : r1) - r0);  // bits [x, y), 0 <= x, y <= 32
+    if (y > x) bits |= (y - x == 32 ? 0xffffffffu : ((1u << (y - x)) - 1u) << x);
+  }
+  ((PQG_G uint32_t*)bitmap)[d] = bits;
+}
+
+// ranges: n pairs [lo, hi) on the device, ascending and disjoint within [0, num_rows]
+int range_bitmap_launch(hipStream_t s, const int64_t* ranges, int n, int64_t num_rows, uint8_t* bitmap) {
+  const int64_t ndw = (num_rows + 31) / 32;
+  if (ndw == 0) return PQG_OK;
+  hipLaunchKernelGGL(k_range_bitmap, dim3((unsigned)((ndw + 255) / 256)), dim3(256), 0, s, ranges, n, ndw, (uint32_t*)bitmap);
+  return hipGetLastError() == hipSuccess ? PQG_OK : PQG_ERR_HIP;
+}
+
 }  // namespace pqg

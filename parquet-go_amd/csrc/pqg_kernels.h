@@ -39,6 +39,9 @@ __global__ void k_cand_link(JobDev* jobs, const int* tile_job, int64_t total_til
 __global__ void k_page_chain(JobDev* jobs, PageDev* pages, const Cand* cands, const int* succ, const int* idx2slot,
                              const int* ok2slot, int* order);
 __global__ void k_scan_pages(JobDev* jobs, PageDev* pages, int n_jobs, int prewalk, int stride);
+// located jobs: one lane per listed page, then their chain (cands: the located region of the candidate table)
+__global__ void k_scan_located(JobDev* jobs, const LocDev* locs, int n_locs, Cand* cands);
+__global__ void k_chain_located(JobDev* jobs, PageDev* pages, const Cand* cands, int* order);
 __global__ void k_page_list(JobDev* jobs, PageDev* pages, int n_jobs, int* list, int list_cap, int* total,
                             int* queues);
 // ---- pqg_crc.hip (K1c)
@@ -129,6 +132,7 @@ int pack_levels_launch(hipStream_t s, const uint8_t* levels, int64_t n, int bw, 
 int filter_launch(hipStream_t s, const flt::Pred& p, const flt::Col& c, const pqg_dictionary* dict, uint32_t* ebits,
                   uint8_t* bitmap, int64_t n, int mode, bool lds, int64_t* seg, int64_t* tot);
 int select_launch(hipStream_t s, const flt::Sel& a, int64_t* seg, int64_t* tot);
+int range_bitmap_launch(hipStream_t s, const int64_t* ranges, int n, int64_t num_rows, uint8_t* bitmap);
 int convert_count_launch(hipStream_t s, const pqg_convert_args* a, int64_t* tot);
 int convert_launch(hipStream_t s, const pqg_convert_args* a);
 

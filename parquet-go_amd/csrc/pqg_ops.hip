@@ -502,6 +502,31 @@ int pqg_select(pqg_ctx* c, pqg_select_args* a) {
   return PQG_OK;
 }
 
+// K9s: row ranges into a row bitmap of pqg_filter's layout (pqg_filter.hip).
+int pqg_range_bitmap(pqg_ctx* c, const int64_t* ranges, int n, int64_t num_rows, uint8_t* bitmap) {
+  if (!c || n < 0 || num_rows < 0 || (n > 0 && !ranges) || (num_rows > 0 && !bitmap) || ((uintptr_t)bitmap & 3))
+    return PQG_ERR_INVALID_ARG;
+  int64_t end = 0;  // of the range before
+  for (int k = 0; k < n; k++) {
+    const int64_t lo = ranges[2 * k], hi = ranges[2 * k + 1];
+    if (lo < end || hi < lo || hi > num_rows) return PQG_ERR_INVALID_ARG;
+    end = hi;
+  }
+  c->flt_ms = 0.f;
+  if (num_rows == 0) return PQG_OK;
+  hipSetDevice(c->device);
+  const size_t bytes = sizeof(int64_t) * 2 * (size_t)n;
+  if (c->flt_buf.grow(bytes + 16)) return PQG_ERR_HIP;
+  if (n > 0 && copy_sync(c, c->flt_buf.p, ranges, bytes, hipMemcpyHostToDevice)) return PQG_ERR_HIP;
+  hipEventRecord(c->ev_flt[0], c->stream);
+  const int e = range_bitmap_launch(c->stream, (const int64_t*)c->flt_buf.p, n, num_rows, bitmap);
+  if (e) return e;
+  hipEventRecord(c->ev_flt[1], c->stream);
+  if (hipStreamSynchronize(c->stream) != hipSuccess) return PQG_ERR_HIP;
+  hipEventElapsedTime(&c->flt_ms, c->ev_flt[0], c->ev_flt[1]);
+  return PQG_OK;
+}
+
 int pqg_last_filter_ms(pqg_ctx* c, float* ms) {
   if (!c || !ms) return PQG_ERR_INVALID_ARG;
   *ms = c->flt_ms;

@@ -121,6 +121,7 @@ const char* pqg_status_string(int s) {
     case PQG_ERR_INVALID_ARG: return "invalid argument";
     case PQG_ERR_HIP: return "HIP runtime error";
     case PQG_ERR_METADATA: return "invalid file metadata";
+    case PQG_ERR_INDEX: return "page index: a located page does not end at offset + size";
   }
   return "unknown";
 }
@@ -239,10 +240,19 @@ static int plan_batch(pqg_ctx* c) {
     d.keep_dict = (in.col.flags & PQG_COL_KEEP_DICT) ? 1 : 0;
     d.entry_width = value_width_of(in.col);
     d.value_width = d.keep_dict ? 4 : d.entry_width;
-    d.no_prewalk = c->many_pages.count(job_key(in)) ? 1 : 0;
+    // a located job (its pages are listed: no tiles, nothing walked): it means the job of its pages back to
+    // back, which has no dictionary page offset
+    d.n_locs = c->n_locs[(size_t)i];
+    d.loc_base = c->loc_base[(size_t)i];
+    const bool located = d.n_locs > 0;
+    d.no_prewalk = !located && c->many_pages.count(job_key(in)) ? 1 : 0;
+    if (located) {
+      d.scan_fallback = 3;
+      d.has_dict_off = 0;
+    }
     const int64_t page_max = (int64_t)1 << 30;
-    const int64_t pcap = region(std::min(in.total_compressed_size / 256 + 16, page_max), std::min(f.pages, page_max), 1,
-                                d.page_cap, d.page_base, page_total);
+    const int64_t pcap = region(located ? (int64_t)d.n_locs + 16 : std::min(in.total_compressed_size / 256 + 16, page_max),
+                                std::min(f.pages, page_max), 1, d.page_cap, d.page_base, page_total);
     const int64_t scap =
         region(std::max<int64_t>(in.num_values_hint, 0) + 64, f.slots, 256, d.slot_cap, d.slot_base, slot_total);
     // variable-length values: chars estimated from the page bytes (dictionary
@@ -277,7 +287,7 @@ static int plan_batch(pqg_ctx* c) {
                d.dchars_cap, d.dchars_base, dchars_total);
     }
     d.tile_base = tile_total;
-    d.n_tiles = (int32_t)((lim + kScanTile - 1) / kScanTile);
+    d.n_tiles = located ? 0 : (int32_t)((lim + kScanTile - 1) / kScanTile);
     tile_total += d.n_tiles;
     c->plan[(size_t)i] = d;
     c->h_jobs[i] = d;
@@ -312,7 +322,8 @@ static int plan_batch(pqg_ctx* c) {
       c->ok2slot.grow(sizeof(int) * (size_t)tile_total * kCandPerTile + 64) ||
       c->cand_pos.grow(sizeof(int64_t) * (size_t)tile_total * kCandPerTile + 64) ||
       c->cand_list.grow(sizeof(int) * (size_t)(tile_total + kQShards) * kCandPerTile + 64) ||
-      c->cands.grow(sizeof(Cand) * (size_t)tile_total * kCandPerTile + 64) ||
+      // the tiles' candidates, then the located region: one record per listed page
+      c->cands.grow(sizeof(Cand) * ((size_t)tile_total * kCandPerTile + c->h_locs.size()) + 64) ||
       c->succ.grow(sizeof(int) * (size_t)tile_total * kCandPerTile + 64) ||
       c->idx2slot.grow(sizeof(int) * (size_t)tile_total * kCandPerTile + 64) ||
       c->order.grow(sizeof(int) * (size_t)page_total + 64) ||
@@ -391,12 +402,19 @@ static int launch_pipeline(pqg_ctx* c) {
   }
   const dim3 tile_grid(n, (unsigned)c->tile_blocks), page_grid(n, (unsigned)c->page_blocks);
   hipLaunchKernelGGL(k_tile_scan, tile_grid, dim3(1024), 0, s, jobs, tcount, tokc, toff, tokoff);
+  // located jobs: one lane per listed page (after k_tile_scan, which resets their results)
+  const int nl = (int)c->h_locs.size();
+  Cand* lcands = cands + nt * kCandPerTile;
+  if (nl > 0)
+    hipLaunchKernelGGL(k_scan_located, dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, s, jobs, (const LocDev*)c->locs.p, nl,
+                       lcands);
   if (nt > 0)
     hipLaunchKernelGGL(k_cand_link, dim3((unsigned)((nt * kCandPerTile + 255) / 256)), dim3(256), 0, s, jobs,
                        (const int*)c->tile_job.p, nt,
                        tcount, toff, tokoff, cands, (int*)c->succ.p, (int*)c->idx2slot.p, (int*)c->ok2slot.p);
   hipLaunchKernelGGL(k_page_chain, page_grid, dim3(1024), 0, s, jobs, pages, cands, (const int*)c->succ.p,
                      (const int*)c->idx2slot.p, (const int*)c->ok2slot.p, (int*)c->order.p);
+  if (nl > 0) hipLaunchKernelGGL(k_chain_located, page_grid, dim3(1024), 0, s, jobs, pages, lcands, (int*)c->order.p);
   hipLaunchKernelGGL(k_scan_pages, dim3(n), dim3(64), 0, s, jobs, pages, n, 0, 0);
   if (c->timed) hipEventRecord(c->ev[1], s);
   hipLaunchKernelGGL(k_page_list, page_grid, dim3(1024), 0, s, jobs, pages, n, list,
@@ -554,7 +572,7 @@ static BatchTraits batch_traits(const pqg_ctx* c, const pqg_chunk_job* jobs, int
   for (int i = 0; i < n_jobs; i++) {
     const pqg_column_desc& d = jobs[i].col;
     const int width = value_width_of(d);
-    b.prewalk |= c->many_pages.find(job_key(jobs[i])) == c->many_pages.end();
+    if (c->n_locs[(size_t)i] == 0) b.prewalk |= c->many_pages.find(job_key(jobs[i])) == c->many_pages.end();
     b.any_snappy |= d.codec == PQG_CODEC_SNAPPY;
     b.any_gzip |= d.codec == PQG_CODEC_GZIP;
     b.any_zstd |= d.codec == PQG_CODEC_ZSTD;
@@ -578,9 +596,23 @@ static BatchTraits batch_traits(const pqg_ctx* c, const pqg_chunk_job* jobs, int
   return b;
 }
 
-int pqg_decode_chunks_async(pqg_ctx* c, const pqg_chunk_job* jobs, int n_jobs) {
+// Submit a batch; `pages`: the located jobs' lists (null: every job is scanned).
+static int submit(pqg_ctx* c, const pqg_chunk_job* jobs, const pqg_chunk_pages* pages, int n_jobs) {
   if (!c || (!jobs && n_jobs) || n_jobs < 0) return PQG_ERR_INVALID_ARG;
   hipSetDevice(c->device);
+  int64_t total_locs = 0;
+  for (int i = 0; pages && i < n_jobs; i++) {
+    const pqg_chunk_pages& p = pages[i];
+    if (p.n < 0 || (p.n > 0 && !p.locs)) return PQG_ERR_INVALID_ARG;
+    int64_t end = 0;  // of the page before
+    for (int k = 0; k < p.n; k++) {
+      const pqg_page_loc& l = p.locs[k];
+      if (l.offset < 0 || l.size <= 0 || l.offset < end || l.offset > jobs[i].data_len - l.size) return PQG_ERR_INVALID_ARG;
+      end = l.offset + l.size;
+    }
+    total_locs += p.n;
+  }
+  if (total_locs > INT32_MAX / 2) return PQG_ERR_INVALID_ARG;
   for (int i = 0; i < n_jobs; i++) {
     const pqg_column_desc& d = jobs[i].col;
     if (d.max_def < 0 || d.max_def > 255 || d.max_rep < 0 || d.max_rep > 255) return PQG_ERR_INVALID_ARG;
@@ -594,15 +626,43 @@ int pqg_decode_chunks_async(pqg_ctx* c, const pqg_chunk_job* jobs, int n_jobs) {
   c->n_jobs = n_jobs;
   c->launches = 0;
   c->force.assign((size_t)n_jobs, Caps());
+  c->h_locs.clear();
+  c->loc_base.assign((size_t)n_jobs, 0);
+  c->n_locs.assign((size_t)n_jobs, 0);
   for (int i = 0; i < n_jobs; i++) {
+    if (pages && pages[i].n > 0) {  // the flat location table, each entry with its job
+      c->loc_base[(size_t)i] = (int64_t)c->h_locs.size();
+      c->n_locs[(size_t)i] = pages[i].n;
+      for (int k = 0; k < pages[i].n; k++) c->h_locs.push_back(LocDev{pages[i].locs[k].offset, pages[i].locs[k].size, i});
+      continue;  // no learned capacities: see pqg_ctx.h
+    }
     auto it = c->learned.find(job_key(jobs[i]));
     if (it != c->learned.end()) c->force[(size_t)i] = it->second;
   }
   c->batch = batch_traits(c, jobs, n_jobs);
   if (n_jobs == 0) return PQG_OK;
+  if (!c->h_locs.empty()) {
+    const size_t bytes = sizeof(LocDev) * c->h_locs.size();
+    if (c->locs.grow(bytes)) return PQG_ERR_HIP;
+    if (copy_sync(c, c->locs.p, c->h_locs.data(), bytes, hipMemcpyHostToDevice)) return PQG_ERR_HIP;
+  }
   int e = plan_batch(c);
   if (e) return e;
   return launch_pipeline(c);
+}
+
+int pqg_decode_chunks_async(pqg_ctx* c, const pqg_chunk_job* jobs, int n_jobs) { return submit(c, jobs, nullptr, n_jobs); }
+
+int pqg_decode_chunks_located_async(pqg_ctx* c, const pqg_chunk_job* jobs, const pqg_chunk_pages* pages, int n_jobs) {
+  if (!pages && n_jobs) return PQG_ERR_INVALID_ARG;
+  return submit(c, jobs, pages, n_jobs);
+}
+
+int pqg_decode_chunks_located(pqg_ctx* c, const pqg_chunk_job* jobs, const pqg_chunk_pages* pages, int n_jobs,
+                              pqg_chunk_result* results) {
+  int e = pqg_decode_chunks_located_async(c, jobs, pages, n_jobs);
+  if (e) return e;
+  return pqg_sync(c, results, n_jobs);
 }
 
 // Copy job results back; grow and re-run chunks that ran out of arena space.
@@ -622,7 +682,7 @@ int pqg_sync(pqg_ctx* c, pqg_chunk_result* results, int n_jobs) {
       if (d.status != PQG_ERR_CAPACITY) continue;
       retry = true;
       c->force[(size_t)i] = caps_of(d, true);
-      c->learned[job_key(c->cur[(size_t)i])] = c->force[(size_t)i];
+      if (d.n_locs == 0) c->learned[job_key(c->cur[(size_t)i])] = c->force[(size_t)i];
     }
     if (!retry || attempt + 1 >= kMaxAttempts) break;
     int e = plan_batch(c);
@@ -632,7 +692,7 @@ int pqg_sync(pqg_ctx* c, pqg_chunk_result* results, int n_jobs) {
   }
   for (int i = 0; i < n; i++) {
     const JobDev& d = c->h_jobs[i];
-    if (d.status != PQG_ERR_CAPACITY && d.scan_fallback != 2) {  // neither walked nor stride-walked by the prewalk
+    if (d.status != PQG_ERR_CAPACITY && d.scan_fallback != 2 && d.n_locs == 0) {  // neither walked nor stride-walked by the prewalk
       if (c->many_pages.size() >= 65536) c->many_pages.clear();  // bounded: a cache, not a record
       const pqg_chunk_job& in = c->cur[(size_t)i];
       c->many_pages[job_key(in)] = true;

@@ -208,9 +208,15 @@ __device__ __forceinline__ bool has_byte_15(uint32_t x) {
 // only if a page link lands on it).  Without the bound, the slowest candidate
 // — garbage that passes the pre-check and reads on through the chunk one
 // dependent granule load at a time — set the kernel's time.
+// kLoc: a located page (k_scan_located).  The index says a header is at p, so the
+// pre-check is not applied, and the page's bytes end at `end` (offset + size):
+// bytes at or past it read as EOF.  The scan's instantiation (kLoc false) reads
+// to the chunk's end.
+template <bool kLoc = false>
 __device__ __forceinline__ void parse_candidate(const JobDev& job, int64_t p, SkipFrame* frames, int16_t* lasts,
-                                             PQG_L uint8_t* win, Cand* out) {
+                                             PQG_L uint8_t* win, Cand* out, int64_t end = 0) {
   Compact<CandSrc> c;
+  const int64_t data_len = kLoc ? end : job.data_len;
   {
     const uintptr_t a0 = (uintptr_t)(job.data + p) & ~(uintptr_t)15;
     const int64_t lo = p - (int64_t)((uintptr_t)(job.data + p) - a0);  // chunk offset of the first granule
@@ -219,18 +225,18 @@ __device__ __forceinline__ void parse_candidate(const JobDev& job, int64_t p, Sk
     // and are zeroed after every load is issued (a load under a branch is
     // waited for inside it)
 #pragma unroll
-    for (int k = 0; k < kCandWin; k++) g[k] = ldg16(lo + 16 * k < job.data_len ? a0 + 16 * k : a0);
+    for (int k = 0; k < kCandWin; k++) g[k] = ldg16(lo + 16 * k < data_len ? a0 + 16 * k : a0);
 #pragma unroll
-    for (int k = 0; k < kCandWin; k++) sts16(win + 16 * k, lo + 16 * k < job.data_len ? g[k] : make_uint4(0, 0, 0, 0));
-    const int64_t whi = lo + 16 * kCandWin < job.data_len ? lo + 16 * kCandWin : job.data_len;
+    for (int k = 0; k < kCandWin; k++) sts16(win + 16 * k, lo + 16 * k < data_len ? g[k] : make_uint4(0, 0, 0, 0));
+    const int64_t whi = lo + 16 * kCandWin < data_len ? lo + 16 * kCandWin : data_len;
     const int64_t lim = p + kCandParseBytes < whi ? p + kCandParseBytes : whi;
-    c.src = CandSrc{win, lo, lim, job.data_len, false};
+    c.src = CandSrc{win, lo, lim, data_len, false};
   }
   // Structural pre-check: every thrift writer of PageHeader emits fields 1, 2,
   // 3 in id order with short-form i32 headers (15 t 15 <varint> 15).  A
   // candidate without that shape is not parsed: it is marked kCOMPLEX, which
   // sends the chunk to the serial walk only if a page link ever lands on it.
-  {
+  if constexpr (!kLoc) {
     int64_t q = p + 3;
     int b = 0x80;
     for (int k = 0; k < 5 && (b & 0x80); k++) b = c.src.get(q++);
@@ -265,7 +271,7 @@ __device__ __forceinline__ void parse_candidate(const JobDev& job, int64_t p, Sk
   Cand cd;
   cd.pos = p;
   cd.next = next;
-  cd.payload = c.pos < job.data_len ? c.pos : job.data_len;  // a failed read stops at the chunk's end
+  cd.payload = c.pos < data_len ? c.pos : data_len;  // a failed read stops at the chunk's end
   cd.comp = comp;
   cd.type = pg.page_type;
   cd.encoding = pg.encoding;
@@ -414,6 +420,107 @@ __global__ void __launch_bounds__(256) k_cand_parse(JobDev* jobs, const int* til
   }
 }
 
+// ---- K1L: located jobs ------------------------------------------------------
+// The pages of a located job are listed by the caller (an OffsetIndex), so nothing
+// is searched: one lane per listed page parses the header at its offset as
+// k_cand_parse parses a candidate (the same window, limits and classify_page), its
+// reads ending at offset + size.  A header that does not end inside the lane's
+// window (long Statistics) or runs out of the lane's stacks is then read by its
+// wave with the serial walk's reader, one such page at a time: the chunk's other
+// pages stay with their lanes.  A page whose own read phase is fine but whose
+// header and body do not end at offset + size fails with kINDEX.  The records go
+// to the located region of the candidate table in list order, and the job's
+// first failing position and its first two dictionary pages are taken with
+// atomics, for k_chain_located.
+__device__ __forceinline__ int64_t lane_i64(int64_t v, int l) {
+  return (int64_t)((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, l) |
+                   (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)v >> 32), l) << 32);
+}
+
+__global__ void __launch_bounds__(256) k_scan_located(JobDev* jobs, const LocDev* locs, int n_locs, Cand* cands) {
+  __shared__ SkipFrame frames[256][kCandFrames];
+  __shared__ int16_t lasts[256][kCandLast];
+  __shared__ __attribute__((aligned(16))) uint8_t wins[256][16 * kCandWin];
+  // the serial reader's window and stacks are the wave's 64 lane regions, once the lanes are done
+  static_assert(64 * 16 * kCandWin >= kWin && 64 * kCandFrames >= kMaxFrames && 64 * kCandLast >= kMaxLast,
+                "a wave's lane regions hold the serial reader's");
+  const int tid = threadIdx.x, lane = lane_id(), w0 = tid - lane;
+  const int64_t i = (int64_t)blockIdx.x * 256 + tid;
+  const bool live = i < n_locs;
+  LocDev lc = locs[live ? i : 0];  // n_locs > 0
+  Cand cd;
+  cd.status = kOK;
+  if (live)
+    parse_candidate<true>(jobs[lc.job], lc.offset, frames[tid], lasts[tid], lds_ptr(wins[tid]), &cd,
+                          lc.offset + lc.size);
+  // a page whose own read phase is fine must end where the index says
+  auto check_end = [](Cand& c, const LocDev& at) {
+    if (c.status == kOK && c.next - at.offset != at.size) {
+      c.status = kINDEX;
+      c.comp = 0;
+    }
+  };
+  if (live) check_end(cd, lc);
+  int st = cd.status, ty = cd.type;  // all that the lane keeps of its record
+  if (live && st != kCOMPLEX) cands[i] = cd;
+  uint64_t todo = __ballot(live && st == kCOMPLEX);
+  __builtin_amdgcn_wave_barrier();
+  while (todo) {  // wave-uniform: every lane reads lane l's page, lane l keeps the record
+    const int l = __builtin_ctzll(todo);
+    todo &= todo - 1;
+    LocDev at;
+    at.job = __builtin_amdgcn_readlane(lc.job, l);
+    at.size = __builtin_amdgcn_readlane(lc.size, l);
+    at.offset = lane_i64(lc.offset, l);
+    const int64_t end = at.offset + at.size;
+    const JobDev& job = jobs[at.job];
+    Compact<WinSrc> c;
+    c.src.w = Window{gconst(job.data), end, kFarAway, lds_ptr(wins[w0])};
+    c.pos = at.offset;
+    c.frames = frames[w0];
+    c.last = lasts[w0];
+    c.nlast = 0;
+    c.last_id = 0;
+    c.bool_set = false;
+    c.bool_val = false;
+    PageHdr h;
+    int e = c.read_page_header(&h);
+    PageDev pg;
+    int64_t next, comp;
+    e = classify_page(job, h, e, c.pos, false, pg, &next, &comp);
+    Cand cs;
+    cs.pos = at.offset;
+    cs.next = next;
+    cs.payload = c.pos < end ? c.pos : end;
+    cs.comp = comp;
+    cs.type = pg.page_type;
+    cs.encoding = pg.encoding;
+    cs.num_values = pg.num_values;
+    cs.csize = pg.csize;
+    cs.usize = pg.usize;
+    cs.def_len = pg.def_len;
+    cs.rep_len = pg.rep_len;
+    cs.def_enc = pg.def_enc;
+    cs.rep_enc = pg.rep_enc;
+    cs.status = e;
+    check_end(cs, at);
+    if (lane == l) {
+      cands[i] = cs;
+      st = cs.status;
+      ty = cs.type;
+    }
+    __builtin_amdgcn_wave_barrier();
+  }
+  if (!live) return;
+  JobDev& job = jobs[lc.job];
+  const int k = (int)(i - job.loc_base);  // the page's position in its job's list
+  if (st != kOK) atomicMin(&job.brk, k);
+  if (st == kOK && ty == 2) {  // the two lowest positions, as k_cand_link takes them
+    const int was = atomicMin(&job.first_dict, k);
+    if (was != INT32_MAX) atomicMin(&job.second_dict, was > k ? was : k);
+  }
+}
+
 // ---- K1b ------------------------------------------------------------------
 // Per-chunk exclusive scans of the tile candidate counts (all, and ok-status).
 // One workgroup per kChunkBlock tiles (grid.x: the job, grid.y: the block; the
@@ -427,6 +534,15 @@ __global__ void __launch_bounds__(1024) k_tile_scan(JobDev* jobs, const int* til
   JobDev& job = jobs[blockIdx.x];
   const int tid = threadIdx.x;
   if (job.scan_fallback == 2) return;  // walked before the scan (k_scan_pages prewalk)
+  if (job.scan_fallback == 3) {  // a located job: no tiles; its results reset for k_scan_located
+    if (blockIdx.y == 0 && tid == 0) {
+      init_job_results(job);
+      job.brk = job.n_locs;
+      job.first_dict = INT32_MAX;
+      job.second_dict = INT32_MAX;
+    }
+    return;
+  }
   const int nt = job.n_tiles;
   const int nblk = (nt + kChunkBlock - 1) / kChunkBlock;
   const int y = blockIdx.y;
@@ -561,9 +677,16 @@ __device__ __forceinline__ bool dict_again(const Cand& c, bool dict_seen) {
   return dict_seen && c.type == 2 && c.status != kTHRIFT;
 }
 
-__global__ void __launch_bounds__(1024) k_page_chain(JobDev* jobs, PageDev* pages, const Cand* cands,
-                                                     const int* succ, const int* idx2slot, const int* ok2slot,
-                                                     int* order) {
+//
+// kLoc: the chain of a located job (k_chain_located).  Its candidates are its listed pages in list
+// order (cands: the located region, job.loc_base), ranks and indices are list positions, and
+// job.brk is the first failing position (k_scan_located): the ok prefix is [0, brk), its last
+// page's successor the failing page at brk, or the end of the list.  Everything after the chain
+// decision (the second-dictionary rule, the prefix sums, the page records, the job's results) is
+// the code the scanned chunks run.
+template <bool kLoc>
+__device__ __forceinline__ void page_chain(JobDev* jobs, PageDev* pages, const Cand* cands, const int* succ,
+                                           const int* idx2slot, const int* ok2slot, int* order) {
   __shared__ int64_t part[17];
   __shared__ int s_n, s_mode, s_cut, s_status, s_dict, s_extra, s_nok;
   const int j = blockIdx.x, y = blockIdx.y;
@@ -571,23 +694,26 @@ __global__ void __launch_bounds__(1024) k_page_chain(JobDev* jobs, PageDev* page
   const int tid = threadIdx.x;
   // the job's fields in one batch, ahead of the barrier
   const int64_t tcs = job.tcs, data_len = job.data_len, tile_base = job.tile_base, page_base = job.page_base;
-  const int n_cands = job.n_cands, n_ok = job.n_ok, b = job.brk, d1 = job.first_dict, d2 = job.second_dict,
-            page_cap = job.page_cap;
+  const int n_cands = job.n_cands, n_ok = kLoc ? job.brk : job.n_ok, b = kLoc ? job.brk - 1 : job.brk,
+            d1 = job.first_dict, d2 = job.second_dict, page_cap = job.page_cap, n_locs = job.n_locs;
   const int64_t lim = tcs < data_len ? tcs : data_len;
   // one read for the whole block: another block of the job may set it meanwhile
   if (tid == 0) s_mode = job.scan_fallback;
   __syncthreads();
-  const bool fb = s_mode != 0;
+  const bool fb = kLoc ? s_mode != 3 : s_mode != 0;  // each kernel takes its own kind of job
   __syncthreads();
   if (fb) return;
-  if (tcs <= 0) return;  // the walk reads nothing: no pages
-  if (lim <= 0 || n_cands == 0) {
-    if (tid == 0) job.scan_fallback = 1;  // a page must start at 0: let the serial walk classify it
-    return;
+  if (!kLoc) {
+    if (tcs <= 0) return;  // the walk reads nothing: no pages
+    if (lim <= 0 || n_cands == 0) {
+      if (tid == 0) job.scan_fallback = 1;  // a page must start at 0: let the serial walk classify it
+      return;
+    }
   }
-  const int64_t cb = tile_base * kCandPerTile;  // the job's candidate-slot base
-  const int* i2s = idx2slot + cb;
-  const int* o2s = ok2slot + cb;
+  const int64_t cb = kLoc ? job.loc_base : tile_base * kCandPerTile;  // the job's candidate-slot base
+  // index -> slot and ok-rank -> slot (a located job's slots are its list positions)
+  auto i2s = [&](int k) { return kLoc ? k : idx2slot[cb + k]; };
+  auto o2s = [&](int k) { return kLoc ? k : ok2slot[cb + k]; };
   // (b = brk < n_ok when index 0 is ok)
   // a chain has at most n_ok + 1 pages: the blocks past them leave at once
   if ((int64_t)y * kChunkBlock > n_ok) return;
@@ -598,18 +724,18 @@ __global__ void __launch_bounds__(1024) k_page_chain(JobDev* jobs, PageDev* page
   // pages: none of them is the chain's last page, which alone can fail or be
   // the second dictionary page).
   Cand spec;
-  const int slot0 = i2s[0];
-  const int slotb = (n_ok > 0 && b >= 0 && b < n_ok) ? o2s[b] : slot0;  // the prefix's last page
+  const int slot0 = i2s(0);
+  const int slotb = (n_ok > 0 && b >= 0 && b < n_ok) ? o2s(b) : slot0;  // the prefix's last page
   {
     const int k = y * kChunkBlock + tid;
-    spec = cands[cb + (n_ok > 0 ? o2s[k < n_ok ? k : n_ok - 1] : slot0)];
+    spec = cands[cb + (n_ok > 0 ? o2s(k < n_ok ? k : n_ok - 1) : slot0)];
   }
-  const int codeb = succ[cb + slotb];
+  const int codeb = kLoc ? (b + 1 < n_locs ? b + 1 : kSuccEnd) : succ[cb + slotb];
   int64_t slot_carry = 0, scratch_carry = 0;
   if (y > 0) {
     int64_t nv = 0, cp = 0;
     for (int q = tid; q < y * kChunkBlock; q += kChunkBlock) {
-      const Cand& c = cands[cb + o2s[q]];  // q < n_ok
+      const Cand& c = cands[cb + o2s(q)];  // q < n_ok
       const int32_t ty = c.type, cs = c.status, cnv = c.num_values;
       cp += c.comp;
       if ((ty == 0 || ty == 3) && cs == kOK) nv += cnv;
@@ -626,7 +752,7 @@ __global__ void __launch_bounds__(1024) k_page_chain(JobDev* jobs, PageDev* page
     s_extra = -1;
     s_nok = 0;
     int n = 0, mode = 0;  // mode 0: ok prefix (+ extra), 1: walked (order[]), 2: fallback
-    if (head.status == kCOMPLEX) {
+    if (!kLoc && head.status == kCOMPLEX) {
       mode = 2;
     } else if (head.status != kOK) {  // the first page fails
       n = 1;
@@ -637,31 +763,31 @@ __global__ void __launch_bounds__(1024) k_page_chain(JobDev* jobs, PageDev* page
         n = s_cut + 1;
         s_nok = n;
       } else {
-        const int code = codeb;  // succ[cb + o2s[b]]
+        const int code = codeb;  // succ[cb + o2s(b)]
         s_nok = b + 1;
         n = b + 1;
-        if (code == kSuccMissing || code == kSuccComplex) {
+        if (!kLoc && (code == kSuccMissing || code == kSuccComplex)) {
           mode = 2;
         } else if (code >= 0) {
-          const int ts = i2s[code];
+          const int ts = i2s(code);
           const Cand& t = cands[cb + ts];
-          if (t.status == kCOMPLEX) {
+          if (!kLoc && t.status == kCOMPLEX) {
             mode = 2;
-          } else if (t.status != kOK) {  // the walk ends on this failing page
+          } else if (kLoc || t.status != kOK) {  // the walk ends on this failing page (a located job's page at brk)
             s_extra = ts;
             if (dict_again(t, d1 <= b)) s_cut = n;
             n++;
-          } else {
+          } else if constexpr (!kLoc) {
             // false ok candidates between pages: block 0 walks the links serially
             // (mode 3: the other blocks leave)
             mode = y == 0 ? 1 : 3;
             int* ord = order + page_base;
-            for (int r = 0; mode == 1 && r <= b && r < page_cap; r++) ord[r] = o2s[r];
+            for (int r = 0; mode == 1 && r <= b && r < page_cap; r++) ord[r] = o2s(r);
             bool dict_seen = d1 <= b;
             int k = b + 1, cur = code;
             while (mode == 1) {
               if (k >= page_cap) { mode = 2; break; }
-              const int sl = i2s[cur];
+              const int sl = i2s(cur);
               const Cand& cd = cands[cb + sl];
               if (cd.status == kCOMPLEX) { mode = 2; break; }
               ord[k++] = sl;
@@ -680,7 +806,7 @@ __global__ void __launch_bounds__(1024) k_page_chain(JobDev* jobs, PageDev* page
         }
       }
     }
-    if (mode == 2) job.scan_fallback = 1;
+    if (!kLoc && mode == 2) job.scan_fallback = 1;  // (a located job never leaves its list: no branch above sets mode 2 for it)
     s_n = n;
     s_mode = mode;
     s_status = kOK;
@@ -701,7 +827,7 @@ __global__ void __launch_bounds__(1024) k_page_chain(JobDev* jobs, PageDev* page
   // Loads are unconditional (the page index clamped to n - 1).
   auto fetch = [&](int k, Cand& c) {
     const int kk = k < n ? k : n - 1;
-    const int sl = mode == 1 ? order[page_base + kk] : (kk < nok ? o2s[kk] : extra);
+    const int sl = mode == 1 ? order[page_base + kk] : (kk < nok ? o2s(kk) : extra);
     c = cands[cb + sl];
   };
   Cand cur = spec;  // block 0 of a walked chain starts at page 0 too
@@ -751,6 +877,19 @@ __global__ void __launch_bounds__(1024) k_page_chain(JobDev* jobs, PageDev* page
     job.num_slots = slot_carry;
     if (n > page_cap || slot_carry > job.slot_cap || scratch_carry > job.scratch_cap) job.status = kCAPACITY;
   }
+}
+
+__global__ void __launch_bounds__(1024) k_page_chain(JobDev* jobs, PageDev* pages, const Cand* cands,
+                                                     const int* succ, const int* idx2slot, const int* ok2slot,
+                                                     int* order) {
+  page_chain<false>(jobs, pages, cands, succ, idx2slot, ok2slot, order);
+}
+
+// cands: the located region of the candidate table (k_scan_located).  The null tables are never read:
+// page_chain<true> maps ranks and indices itself, and the branches that follow `succ` or hand a job to
+// the serial walk (a walked chain, a kCOMPLEX link) are compiled out of it.
+__global__ void __launch_bounds__(1024) k_chain_located(JobDev* jobs, PageDev* pages, const Cand* cands, int* order) {
+  page_chain<true>(jobs, pages, cands, nullptr, nullptr, nullptr, order);
 }
 
 // ---- K1e: the serial walk (fallback) — one wave per chunk ------------------

@@ -33,6 +33,17 @@ def lib():
         "pqg_decode_chunks_async": ([P, C.POINTER(abi.ChunkJob), I], I),
         "pqg_sync": ([P, C.POINTER(abi.ChunkResult), I], I),
         "pqg_decode_chunks": ([P, C.POINTER(abi.ChunkJob), I, C.POINTER(abi.ChunkResult)], I),
+        "pqg_decode_chunks_located_async": ([P, C.POINTER(abi.ChunkJob), C.POINTER(abi.ChunkPages), I], I),
+        "pqg_decode_chunks_located": ([P, C.POINTER(abi.ChunkJob), C.POINTER(abi.ChunkPages), I,
+                                       C.POINTER(abi.ChunkResult)], I),
+        "pqg_file_chunk_index": ([P, I, I, C.POINTER(abi.IndexRanges)], I),
+        "pqg_parse_offset_index": ([C.c_char_p, I64, C.POINTER(abi.PageLoc), I], I),
+        "pqg_column_index_parse": ([C.c_char_p, I64, C.POINTER(P)], I),
+        "pqg_column_index_pages": ([P], I),
+        "pqg_column_index_page": ([P, I, C.POINTER(abi.ChunkStats), C.POINTER(C.c_int32)], I),
+        "pqg_column_index_boundary_order": ([P], I),
+        "pqg_column_index_free": ([P], None),
+        "pqg_range_bitmap": ([P, C.POINTER(I64), I, I64, P], I),
         "pqg_get_pages": ([P, I, C.POINTER(abi.PageInfo), I], I),
         "pqg_get_dictionary": ([P, I, C.POINTER(abi.Dictionary)], I),
         "pqg_last_timings": ([P, C.POINTER(C.c_float), I], I),
@@ -95,4 +106,7 @@ EXPORTED = [
     "pqg_get_dictionary", "pqg_file_chunk_stats", "pqg_filter", "pqg_select", "pqg_last_filter_ms",
     "pqg_convert", "pqg_last_convert_ms", "pqg_file_column_logical",
     "pqg_assemble_structs", "pqg_file_schema_node_kind",
+    "pqg_decode_chunks_located_async", "pqg_decode_chunks_located", "pqg_range_bitmap",
+    "pqg_file_chunk_index", "pqg_parse_offset_index", "pqg_column_index_parse", "pqg_column_index_pages",
+    "pqg_column_index_page", "pqg_column_index_boundary_order", "pqg_column_index_free",
 ]

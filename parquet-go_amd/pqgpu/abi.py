@@ -46,6 +46,7 @@ STATUS = {
     -22: "HIP",
     -23: "METADATA",
     -24: "NOT_BUILT",
+    -25: "INDEX",
 }
 OK = 0
 ERR_CAPACITY = -20
@@ -84,6 +85,16 @@ class ChunkJob(C.Structure):
 
 
 QUIRK_Q1_PAGE_NILS, QUIRK_Q2_DICT_ALIAS = 1, 2
+
+
+class PageLoc(C.Structure):
+    """pqg_page_loc (include/pqgpu.h): one page of a located decode."""
+    _fields_ = [("offset", C.c_int64), ("size", C.c_int32), ("reserved", C.c_int32), ("first_row", C.c_int64)]
+
+
+class ChunkPages(C.Structure):
+    """pqg_chunk_pages (include/pqgpu.h): the page list of one job (n == 0: the job is scanned)."""
+    _fields_ = [("locs", C.POINTER(PageLoc)), ("n", C.c_int32), ("reserved", C.c_int32)]
 
 
 class PageJob(C.Structure):
@@ -239,6 +250,12 @@ class ChunkStats(C.Structure):
     """pqg_chunk_stats (include/pqgpu.h): ColumnMetaData.statistics of one chunk."""
     _fields_ = [("min_value", C.c_void_p), ("max_value", C.c_void_p), ("min_len", C.c_int32),
                 ("max_len", C.c_int32), ("null_count", C.c_int64)]
+
+
+class IndexRanges(C.Structure):
+    """pqg_index_ranges (include/pqgpu.h): where a chunk's page indexes lie in the file (length 0: none)."""
+    _fields_ = [("offset_index_offset", C.c_int64), ("column_index_offset", C.c_int64),
+                ("offset_index_length", C.c_int32), ("column_index_length", C.c_int32)]
 
 
 # pqg_filter operators and combine modes

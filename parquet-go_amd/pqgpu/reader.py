@@ -29,6 +29,39 @@ def _check(rc, what):
         raise PqgError(rc, what)
 
 
+class PageIndex:
+    """The page index of one column chunk (ParquetFile.page_index).
+
+    locations      [(offset, size, first_row)] per page of the OffsetIndex: absolute file offset of the
+                   page header, header + body bytes, first row of the page in its row group
+    null_pages, min_values, max_values, null_counts, boundary_order: the ColumnIndex, None when the
+                   chunk has only an OffsetIndex (null_counts also when the index has none); a null
+                   page's bounds are None, the others physical little-endian bytes or raw strings"""
+
+    def __init__(self, locations, rows, column=None):
+        self.locations = locations
+        self.rows = rows  # of the row group
+        self.null_pages = self.min_values = self.max_values = self.null_counts = self.boundary_order = None
+        if column is not None:
+            self.null_pages, self.min_values, self.max_values, self.null_counts, self.boundary_order = column
+
+    def page_rows(self, page):
+        """[first, end) rows of a page."""
+        end = self.locations[page + 1][2] if page + 1 < len(self.locations) else self.rows
+        return self.locations[page][2], end
+
+    def stats(self, page):
+        """(min, max, null_count) of a page, as filters.term_rules_out takes a chunk's: (None, None, -1)
+        without a ColumnIndex; an all-null page reports its row count as its null count."""
+        if self.null_pages is None:
+            return None, None, -1
+        nulls = self.null_counts[page] if self.null_counts is not None else -1
+        if self.null_pages[page]:
+            lo, hi = self.page_rows(page)
+            return None, None, hi - lo
+        return self.min_values[page], self.max_values[page], nulls
+
+
 class ParquetFile:
     """Footer + schema of a parquet file (readFileMetaData file_meta.go:14-62).
 
@@ -135,6 +168,64 @@ class ParquetFile:
         lo = C.string_at(st.min_value, st.min_len) if st.min_value else None
         hi = C.string_at(st.max_value, st.max_len) if st.max_value else None
         return lo, hi, int(st.null_count)
+
+    def page_index(self, rg, col):
+        """The PageIndex of a chunk, None when the file holds no OffsetIndex for it.  The index bytes of
+        a row group are fetched with one read_range on first use and cached.  A ColumnIndex that does
+        not parse, or whose page count is not the OffsetIndex's, is left out (the locations stand);
+        an OffsetIndex that does not parse raises PqgError(METADATA)."""
+        cache = self.__dict__.setdefault("_page_index", {})
+        if (rg, col) in cache:
+            return cache[(rg, col)]
+        L = lib()
+        raw = self.__dict__.setdefault("_index_bytes", {})
+        if rg not in raw:  # one range over every index of the row group
+            rs = []
+            for c in range(self.num_columns):
+                ir = abi.IndexRanges()
+                _check(L.pqg_file_chunk_index(self._h, rg, c, C.byref(ir)), "pqg_file_chunk_index")
+                rs.append(ir)
+            spans = [(r.offset_index_offset, r.offset_index_offset + r.offset_index_length) for r in rs
+                     if r.offset_index_length] + \
+                    [(r.column_index_offset, r.column_index_offset + r.column_index_length) for r in rs
+                     if r.column_index_length]
+            lo = min((a for a, _ in spans), default=0)
+            hi = max((b for _, b in spans), default=0)
+            raw[rg] = (rs, lo, bytes(self.read_range(lo, hi)))
+            self.index_bytes_read = getattr(self, "index_bytes_read", 0) + (hi - lo)
+        rs, lo, blob = raw[rg]
+        ir = rs[col]
+        out = None
+        if ir.offset_index_length:
+            b = blob[ir.offset_index_offset - lo:ir.offset_index_offset - lo + ir.offset_index_length]
+            n = L.pqg_parse_offset_index(b, len(b), None, 0)
+            if n < 0 or len(b) != ir.offset_index_length:
+                raise PqgError(n if n < 0 else abi.STATUS_CODES["METADATA"], "pqg_parse_offset_index")
+            locs = (abi.PageLoc * max(n, 1))()
+            L.pqg_parse_offset_index(b, len(b), locs, n)
+            column = None
+            if ir.column_index_length:
+                cb = blob[ir.column_index_offset - lo:ir.column_index_offset - lo + ir.column_index_length]
+                h = C.c_void_p()
+                if L.pqg_column_index_parse(cb, len(cb), C.byref(h)) == 0:
+                    try:
+                        if L.pqg_column_index_pages(h) == n:
+                            nulls, mins, maxs, counts = [], [], [], []
+                            for k in range(n):
+                                st, np_ = abi.ChunkStats(), C.c_int32()
+                                _check(L.pqg_column_index_page(h, k, C.byref(st), C.byref(np_)), "pqg_column_index_page")
+                                nulls.append(bool(np_.value))
+                                mins.append(C.string_at(st.min_value, st.min_len) if st.min_value else None)
+                                maxs.append(C.string_at(st.max_value, st.max_len) if st.max_value else None)
+                                counts.append(int(st.null_count))
+                            column = (nulls, mins, maxs, counts if all(x >= 0 for x in counts) and n else None,
+                                      L.pqg_column_index_boundary_order(h))
+                    finally:
+                        L.pqg_column_index_free(h)
+            out = PageIndex([(int(locs[k].offset), int(locs[k].size), int(locs[k].first_row)) for k in range(n)],
+                            self.row_group_rows(rg), column)
+        cache[(rg, col)] = out
+        return out
 
     def host_job(self, rg, col):
         """A chunk job whose data pointer is HOST memory (for the CPU oracle)."""
@@ -330,6 +421,35 @@ class GpuDecoder:
         _check(self.L.pqg_decode_chunks(self.ctx, arr, n, res), "pqg_decode_chunks")
         return [res[i] for i in range(n)]
 
+    def decode_located(self, jobs, locations):
+        """pqg_decode_chunks_located: `locations[i]` lists job i's pages as (offset, size) pairs
+        relative to the job's data, in ascending order; None or an empty list: the job is scanned.
+        A listed page is decoded where the list says it is and no chunk byte is searched for page
+        headers; a page that does not end at offset + size is the read-phase error INDEX (-25)."""
+        n = len(jobs)
+        arr = (abi.ChunkJob * max(n, 1))(*jobs)
+        res = (abi.ChunkResult * max(n, 1))()
+        pages = (abi.ChunkPages * max(n, 1))()
+        keep = []
+        for i, locs in enumerate(locations):
+            locs = list(locs or ())
+            if locs:
+                t = (abi.PageLoc * len(locs))()
+                for k, l in enumerate(locs):
+                    t[k].offset, t[k].size = int(l[0]), int(l[1])
+                keep.append(t)
+                pages[i].locs = t
+                pages[i].n = len(locs)
+        _check(self.L.pqg_decode_chunks_located(self.ctx, arr, pages, n, res), "pqg_decode_chunks_located")
+        return [res[i] for i in range(n)]
+
+    def range_bitmap(self, ranges, num_rows, bitmap_ptr):
+        """pqg_range_bitmap: the rows of the ascending, disjoint `ranges` ((lo, hi) pairs) as a row bitmap of
+        pqg_filter's layout at the device pointer `bitmap_ptr` (4 * ceil(num_rows / 32) bytes)."""
+        flat = np.ascontiguousarray(np.asarray(list(ranges), dtype=np.int64).reshape(-1))
+        _check(self.L.pqg_range_bitmap(self.ctx, flat.ctypes.data_as(C.POINTER(C.c_int64)), len(flat) // 2, num_rows,
+                                       C.c_void_p(bitmap_ptr)), "pqg_range_bitmap")
+
     def pages(self, job_index, cap=1 << 20):
         buf = (abi.PageInfo * cap)()
         k = self.L.pqg_get_pages(self.ctx, job_index, buf, cap)
@@ -374,7 +494,8 @@ class GpuDecoder:
         return ms.value
 
     def debug_job(self, job_index):
-        """(serial_walk, candidates, pages, scratch_bytes, pipeline_launches) of the last decode."""
+        """(serial_walk, candidates, pages, scratch_bytes, pipeline_launches) of the last decode;
+        serial_walk is 3 (with 0 candidates) for a located job."""
         out = (C.c_int64 * 5)()
         k = self.L.pqg_debug_job(self.ctx, job_index, out, 5)
         if k < 0:
@@ -752,7 +873,122 @@ def span_jobs(pf: ParquetFile, specs, dec, to_eof=()):
     return jobs, dev, total
 
 
-def decode_spans(pf: ParquetFile, specs, dec, keep_dict=()):
+def _merge(ranges):
+    """Sorted, disjoint, non-empty row ranges covering `ranges` (adjacent ones joined)."""
+    out = []
+    for a, b in sorted(r for r in ranges if r[1] > r[0]):
+        if out and a <= out[-1][1]:
+            out[-1] = (out[-1][0], max(out[-1][1], b))
+        else:
+            out.append((a, b))
+    return out
+
+
+def _intersect(x, y):
+    """The rows in both of two sorted lists of disjoint row ranges."""
+    out, i, j = [], 0, 0
+    while i < len(x) and j < len(y):
+        a, b = max(x[i][0], y[j][0]), min(x[i][1], y[j][1])
+        if b > a:
+            out.append((a, b))
+        if x[i][1] < y[j][1]:
+            i += 1
+        else:
+            j += 1
+    return out
+
+
+def located_jobs(pf: ParquetFile, specs, dec, pages=None):
+    """Chunk jobs for (rg, col) pairs decoded by page location where the file has an OffsetIndex: of
+    such a chunk only the listed pages are uploaded, packed, with their locations rebased to the packed
+    bytes (the dictionary page, the gap between the chunk's start and its first data page, goes first).  `pages`: {spec index:
+    sorted data page numbers} to list only those (default: all).  Chunks without an index are uploaded
+    whole and scanned.  Returns (jobs, location lists (None: scanned), device buffer, bytes uploaded,
+    (pages listed, pages in all) per spec)."""
+    parts, plan = [], []
+    for i, (rg, c) in enumerate(specs):
+        m = pf.chunk_meta(rg, c)
+        start = max(0, min(m.start, pf.size))
+        pi = pf.page_index(rg, c)
+        if pi is None or not pi.locations:
+            plan.append((m, [(start, max(0, min(m.start + m.total_compressed_size, pf.size)))], None, (0, 0)))
+            continue
+        want = range(len(pi.locations)) if pages is None or i not in pages else pages[i]
+        ranges = []
+        first = pi.locations[0][0]
+        if start < first:  # whatever lies before the first data page: the dictionary page, with or
+            ranges.append((start, first))  # without a dictionary_page_offset in the footer
+        ranges += [(pi.locations[k][0], pi.locations[k][0] + pi.locations[k][1]) for k in want]
+        plan.append((m, ranges, True, (len(want), len(pi.locations))))
+    flat = []  # in packing order; neighbours that touch in the file are one copy
+    for _, ranges, _, _ in plan:
+        for lo, hi in ranges:
+            if flat and flat[-1][1] == lo:
+                flat[-1] = (flat[-1][0], hi)
+            else:
+                flat.append((lo, hi))
+    total = sum(hi - lo for lo, hi in flat)
+    if pf._buf is not None:
+        dev = dec.upload_ranges(pf._buf, flat)
+    else:
+        host = np.empty(max(total, 1), dtype=np.uint8)
+        at = 0
+        for lo, hi in flat:
+            host[at:at + hi - lo] = pf.read_range(lo, hi)
+            at += hi - lo
+        dev = dec.upload(host)
+    jobs, lists, counts, at = [], [], [], 0
+    for (rg, c), (m, ranges, located, cnt) in zip(specs, plan):
+        size = sum(hi - lo for lo, hi in ranges)
+        job = abi.ChunkJob()
+        job.col = pf.columns[c].desc
+        job.col.codec = m.codec
+        job.total_compressed_size = m.total_compressed_size if not located else size
+        job.data_page_offset = m.data_page_offset - m.start
+        job.num_values_hint = m.num_values
+        job.total_uncompressed_size = m.total_uncompressed_size
+        job.has_dict_page_offset = m.has_dict_page_offset if not located else 0
+        job.data = dev + at
+        job.data_len = size
+        locs, o = None, 0
+        if located:
+            locs = []
+            for lo, hi in ranges:
+                locs.append((o, hi - lo))
+                o += hi - lo
+        jobs.append(job)
+        lists.append(locs)
+        counts.append(cnt)
+        at += size
+    return jobs, lists, dev, total, counts
+
+
+def _decode_spans_located(pf, specs, dec, keep_dict, info):
+    """decode_spans with use_page_index: the chunks that have an OffsetIndex by location (all pages,
+    the dictionary page first), the others scanned, in one batch.  A chunk that comes back INDEX (its
+    index is wrong) sends the batch to the scan once more, and so does any other failing chunk: the
+    scanned path has second batches of its own (NOT_DICT, EOF, SIZE), and what it reports for a chunk
+    that does not decode is what the caller gets."""
+    jobs, lists, dev, nbytes, counts = located_jobs(pf, specs, dec)
+    for i, (_, c) in enumerate(specs):
+        if c in keep_dict:
+            jobs[i].col.flags |= abi.COL_KEEP_DICT
+    res = dec.decode_located(jobs, lists)
+    code = abi.STATUS_CODES
+    bad = [i for i, r in enumerate(res) if lists[i] is not None and r.status == code["INDEX"]]
+    if info is not None:
+        info["located"] = {specs[i]: lists[i] is not None and i not in bad for i in range(len(specs))}
+        info["fell_back"] = [specs[i] for i in bad]
+        info["pages_decoded"] = sum(a for a, _ in counts)
+        info["pages_total"] = sum(b for _, b in counts)
+    if not any(r.status != 0 for r in res):
+        return res, dev, nbytes
+    dec.free(dev)
+    res, dev, nb2 = decode_spans(pf, specs, dec, keep_dict)
+    return res, dev, nbytes + nb2
+
+
+def decode_spans(pf: ParquetFile, specs, dec, keep_dict=(), use_page_index=False, info=None):
     """span_jobs + pqg_decode_chunks for (rg, col) pairs.  The chunks of the columns in
     `keep_dict` (column indices) are decoded with abi.COL_KEEP_DICT; those that come back
     NOT_DICT (a data page that is not dictionary encoded: a writer's fallback) are decoded
@@ -763,7 +999,13 @@ def decode_spans(pf: ParquetFile, specs, dec, keep_dict=()):
     reads whole: chunk_reader.go:212-280) is decoded again with the bytes to the
     end of the file, in a second batched call (device outputs are only valid
     until the next decode on `dec`).  Returns (results, device buffer, bytes
-    uploaded); the caller frees the buffer after using the outputs."""
+    uploaded); the caller frees the buffer after using the outputs.
+    use_page_index: chunks with an OffsetIndex are decoded by location (_decode_spans_located);
+    info: a dict that receives located / fell_back / pages_decoded / pages_total."""
+    if use_page_index:
+        return _decode_spans_located(pf, specs, dec, keep_dict, info)
+    if info is not None:
+        info.update(located={s: False for s in specs}, fell_back=[], pages_decoded=0, pages_total=0)
     jobs, dev, nbytes = span_jobs(pf, specs, dec)
     keep = {i for i, (_, c) in enumerate(specs) if c in keep_dict}
     for i in keep:
@@ -815,10 +1057,19 @@ class FileReader:
     typed literals (pqgpu.filters.literal), order FLBA decimals signed, and compare an INT96 column
     as int64 nanoseconds since the epoch (such a predicate column is decoded materialised, whatever
     read_dictionary says); a predicate on a BYTE_ARRAY decimal raises PqgError(UNSUPPORTED).
-    next_row ignores the option.  Off (the default), every method returns what it always did."""
+    next_row ignores the option.  Off (the default), every method returns what it always did.
+    `use_page_index`: chunks for which the file holds an OffsetIndex are decoded by page location
+    (pqg_decode_chunks_located: no chunk byte is scanned for page headers) in every reader; chunks
+    without one are scanned, and a chunk whose index proves wrong (INDEX) is decoded again by the
+    scan.  read_row_group then also uploads and decodes only the pages that its `rows=` range and
+    the ColumnIndex bounds of its `filters=` cannot rule out.  `last_read` tells what the last
+    decode did: pages_total, pages_decoded, located {(rg, col): bool}, fell_back [(rg, col)] and,
+    after read_row_group, row_ranges (the rows that were decoded and kept before the filter ran)."""
 
     def __init__(self, source, *columns, device=0, decoder=None, verify_crc=False, read_dictionary=(),
-                 convert_logical=False, int96_unit="ns"):
+                 convert_logical=False, int96_unit="ns", use_page_index=False):
+        self.use_page_index = bool(use_page_index)
+        self.last_read = {}
         if int96_unit not in abi.UNITS:
             raise ValueError("int96_unit: one of %s" % ", ".join(sorted(abi.UNITS)))
         self.convert_logical = bool(convert_logical)
@@ -837,6 +1088,12 @@ class FileReader:
         self.uploaded_bytes = 0   # H2D bytes so far (projection pushdown check)
         self._rows = None         # NextRow state (pqgpu.rows.RowReader)
         self._held = None         # chunk bytes decode_row_groups left on the device (in-place dictionaries)
+
+    def _decode_spans(self, specs, keep_dict):
+        info = {}
+        out = decode_spans(self.file, specs, self.dec, keep_dict, self.use_page_index, info)
+        self.last_read = info
+        return out
 
     def _release(self):
         """Free the chunk bytes the last decode_row_groups kept for its dictionaries."""
@@ -914,7 +1171,7 @@ class FileReader:
         specs = [(rg, c) for rg in rgs for c in self.selected]
         if not specs:
             return []
-        res, dev, nbytes = decode_spans(self.file, specs, self.dec, self.keep_dict)
+        res, dev, nbytes = self._decode_spans(specs, self.keep_dict)
         self.uploaded_bytes += nbytes
         if any(r.col_flags & abi.COL_KEEP_DICT for r in res):
             self._held = dev
@@ -922,16 +1179,18 @@ class FileReader:
             self.dec.free(dev)
         return [(rg, c, r) for (rg, c), r in zip(specs, res)]
 
-    def read_row_group(self, rg, filters=None):
+    def read_row_group(self, rg, filters=None, rows=None):
         """One row group's selected columns, downloaded: {path: DecodedColumn}.  `filters`
-        (pyarrow's DNF, pqgpu.filters) keeps only the rows that pass: see _read_filtered."""
-        if filters is not None:
-            return self._read_filtered(rg, filters)
+        (pyarrow's DNF, pqgpu.filters) keeps only the rows that pass: see _read_filtered.
+        `rows`: (start, stop) or a slice of the row group's rows (flat columns only): only those
+        rows come back, and with use_page_index only the pages that hold them are uploaded."""
+        if filters is not None or rows is not None:
+            return self._read_filtered(rg, filters, rows)
         self._release()
         specs = [(rg, c) for c in self.selected]
         if not specs:
             return {}
-        res, dev, nbytes = decode_spans(self.file, specs, self.dec, self.keep_dict)
+        res, dev, nbytes = self._decode_spans(specs, self.keep_dict)
         self.uploaded_bytes += nbytes
         try:
             return {self.file.columns[c].path.decode(): self._download(r, i, c)
@@ -939,7 +1198,133 @@ class FileReader:
         finally:
             self.dec.free(dev)
 
-    def _read_filtered(self, rg, filters):
+    def _row_ranges(self, rg, dnf, rows):
+        """The sorted, disjoint row ranges R a planned read keeps before its filter runs: `rows`, and
+        with use_page_index and filters, intersected with the union over the conjunctions of the rows
+        of the pages that no term's ColumnIndex bounds rule out (conservative, as prune_row_groups)."""
+        from . import filters as F
+        n = self.file.row_group_rows(rg)
+        if rows is None:
+            R = [(0, n)]
+        else:
+            if isinstance(rows, slice):
+                if rows.step not in (None, 1):
+                    raise ValueError("rows: a slice of step 1")
+                lo, hi, _ = rows.indices(n)
+            else:
+                lo, hi = rows
+                lo, hi = max(0, min(int(lo), n)), max(0, min(int(hi), n))
+            R = [(lo, hi)] if hi > lo else []
+        if dnf is not None and self.use_page_index:
+            keep = []
+            for terms in dnf:
+                conj = [(0, n)]
+                for t in terms:
+                    c = self.file.column_index(t.column)
+                    desc, lt = self.file.columns[c].desc, self._logical(c)
+                    pi = self.file.page_index(rg, c)
+                    if pi is None or pi.null_pages is None or (lt is not None and desc.physical_type == abi.INT96):
+                        continue  # never prunes
+                    spans = []
+                    for k in range(len(pi.locations)):
+                        a, b = pi.page_rows(k)
+                        if b > a and not F.term_rules_out(desc, t, pi.stats(k), b - a, lt):
+                            spans.append((a, b))
+                    conj = _intersect(conj, _merge(spans))
+                keep += conj
+            R = _intersect(R, _merge(keep))
+        return R
+
+    def _decode_planned(self, rg, cols, keep_named, R, temps, sels):
+        """Decode the chunks of `cols` for the rows R of row group rg and trim each to R: with
+        use_page_index only the pages meeting R (and the dictionary page) are uploaded, packed, and
+        decoded by location; pqg_range_bitmap + pqg_select then drop the rows of those pages outside R.
+        Returns ([ChunkResult whose arrays hold exactly R's rows], device buffer)."""
+        n = self.file.row_group_rows(rg)
+        specs = [(rg, c) for c in cols]
+        info = {}
+        whole = [(0, n)]
+        spans = {i: whole for i in range(len(cols))}
+        res = None
+        if self.use_page_index and R != whole:
+            pages = {}
+            for i, c in enumerate(cols):
+                pi = self.file.page_index(rg, c)
+                if pi is not None and pi.locations:
+                    pages[i] = [k for k in range(len(pi.locations))
+                                if _intersect([pi.page_rows(k)], R)]
+                    spans[i] = _merge([pi.page_rows(k) for k in pages[i]])
+            jobs, lists, dev, nbytes, counts = located_jobs(self.file, specs, self.dec, pages)
+            for i, c in enumerate(cols):
+                if c in keep_named:
+                    jobs[i].col.flags |= abi.COL_KEEP_DICT
+            res = self.dec.decode_located(jobs, lists)
+            code = abi.STATUS_CODES
+            bad = [i for i, r in enumerate(res) if lists[i] is not None and r.status == code["INDEX"]]
+            info = dict(located={specs[i]: lists[i] is not None and i not in bad for i in range(len(specs))},
+                        fell_back=[specs[i] for i in bad], pages_decoded=sum(a for a, _ in counts),
+                        pages_total=sum(b for _, b in counts))
+            if any(r.status != 0 for r in res):
+                self.dec.free(dev)  # the scan, on the whole chunks
+                self.uploaded_bytes += nbytes
+                res = None
+                spans = {i: whole for i in range(len(cols))}
+        if res is None:
+            fell = info.get("fell_back", [])
+            res, dev, nbytes = decode_spans(self.file, specs, self.dec, keep_named, self.use_page_index and not fell, info)
+            if fell:
+                info["fell_back"] = fell
+        self.uploaded_bytes += nbytes
+        info["row_ranges"] = list(R)
+        self.last_read = info
+        out = []
+        try:
+            for i, (c, r) in enumerate(zip(cols, res)):
+                if r.status != 0:
+                    raise PqgError(r.status, "column %s of row group %d" % (self.file.columns[c].path.decode(), rg))
+                have = sum(b - a for a, b in spans[i])
+                if r.num_slots != have:
+                    raise PqgError(abi.STATUS_CODES["INVALID_ARG"], "row group %d: column %s has %d rows, not %d"
+                                   % (rg, self.file.columns[c].path.decode(), r.num_slots, have))
+                if spans[i] == R:
+                    out.append(r)
+                    continue
+                rel, at = [], 0  # R in the numbering of the decoded rows
+                for a, b in spans[i]:
+                    rel += [(at + x - a, at + y - a) for x, y in _intersect([(a, b)], R)]
+                    at += b - a
+                bm = self.dec.alloc((have + 31) // 32 * 4)
+                temps.append(bm)
+                self.dec.range_bitmap(rel, have, bm)
+                sel = self.dec.select(bm, r.def_levels, r.values, r.offsets, have, r.num_values, r.values_bytes,
+                                      self.file.columns[c].desc.max_def, r.value_width)
+                sels.append(sel)
+                t = abi.ChunkResult.from_buffer_copy(r)
+                t.def_levels, t.values, t.offsets = sel.out_def_levels, sel.out_values, sel.out_offsets
+                t.num_slots, t.num_values, t.values_bytes = sel.rows_out, sel.values_out, sel.bytes_out
+                out.append(t)
+        except Exception:
+            for a in sels:
+                self.dec.free_select(a)
+            for p in temps:
+                self.dec.free(p)
+            del sels[:], temps[:]
+            self.dec.free(dev)
+            raise
+        return out, dev
+
+    def _no_rows(self, cols):
+        """Zero-row columns: what a read of no rows returns, with nothing uploaded or decoded."""
+        out = {}
+        for c in cols:
+            d = self.file.columns[c].desc
+            w = abi.FIXED_WIDTH.get(d.physical_type, max(d.type_length, 0) if d.physical_type == 7 else 0)
+            out[self.file.columns[c].path.decode()] = DecodedColumn(
+                0, -1, 0, 0, w, np.zeros(0, np.uint8) if d.max_def > 0 else None, None, np.zeros(0, np.uint8), [],
+                np.zeros(1, np.int64) if w == 0 else None, logical=self._logical(c))
+        return out
+
+    def _read_filtered(self, rg, filters, rows=None):
         """read_row_group with filters: a list of (column, op, value) tuples (AND) or a list of
         such lists (OR of ANDs); op is one of == = != < <= > >= in not in, or "is" / "is not" with
         None.  The predicate columns (selected or not) are decoded in the same batch as the
@@ -950,10 +1335,12 @@ class FileReader:
         chunk that fell back is filtered materialised.  A repeated column, selected or in a
         predicate, raises PqgError(UNSUPPORTED) before any GPU work; a chunk that does not decode
         raises its status, a value that does not fit its column's type ValueError.  No row group
-        is pruned here (prune_row_groups)."""
+        is pruned here (prune_row_groups).  `rows` and use_page_index: the rows R of _row_ranges
+        are decoded and trimmed first (_decode_planned), and the predicates run on them; without
+        filters the trimmed columns are the result."""
         from . import filters as F
-        dnf = F.parse(filters)
-        pred_cols = [self.file.column_index(name) for name in F.columns_of(dnf)]
+        dnf = F.parse(filters) if filters is not None else None
+        pred_cols = [self.file.column_index(name) for name in F.columns_of(dnf)] if dnf is not None else []
         cols = list(self.selected) + [c for c in pred_cols if c not in self.selected]
         for c in cols:
             if self.file.columns[c].desc.max_rep > 0:
@@ -971,11 +1358,18 @@ class FileReader:
                 c in pred_cols and self.file.columns[c].desc.physical_type == abi.INT96))
         self._release()
         specs = [(rg, c) for c in cols]
-        res, dev, nbytes = decode_spans(self.file, specs, self.dec, keep_named)
-        self.uploaded_bytes += nbytes
+        R = self._row_ranges(rg, dnf, rows)
+        if not R:
+            self.last_read = dict(located={s: False for s in specs}, fell_back=[], pages_decoded=0, pages_total=0,
+                                  row_ranges=[])
+            return self._no_rows(self.selected)
         job = {c: i for i, c in enumerate(cols)}
-        temps = []
+        temps, sels = [], []
+        res, dev = self._decode_planned(rg, cols, keep_named if dnf is not None else self.keep_dict, R, temps, sels)
         try:
+            if dnf is None:  # a row-range read: the trimmed columns as they are
+                return {self.file.columns[c].path.decode(): self._download(r, i, c)
+                        for i, (c, r) in enumerate(zip(cols, res))}
             for (_, c), r in zip(specs, res):
                 if r.status != 0:
                     raise PqgError(r.status, "column %s of row group %d" % (self.file.columns[c].path.decode(), rg))
@@ -1072,6 +1466,8 @@ class FileReader:
                     self.dec.pages(i), offs, dictionary=dic, logical=self._logical(c))
             return out
         finally:
+            for a in sels:
+                self.dec.free_select(a)
             for p in temps:
                 self.dec.free(p)
             self.dec.free(dev)
@@ -1123,7 +1519,7 @@ class FileReader:
                 raise PqgError(abi.STATUS_CODES["UNSUPPORTED"], "column %s: %d list depths (at most %d)"
                                % (self.file.columns[c].path.decode(), len(ed), abi.MAX_LIST_DEPTH))
             thr[c] = (ld, ed)
-        res, dev, nbytes = decode_spans(self.file, specs, self.dec, self.keep_dict)
+        res, dev, nbytes = self._decode_spans(specs, self.keep_dict)
         self.uploaded_bytes += nbytes
         try:
             return {self.file.columns[c].path.decode(): self._nested_leaf(rg, i, c, r, thr[c])
@@ -1186,7 +1582,7 @@ class FileReader:
             return tree.build(root, {}, {}, rows)
         thr = {c: leaf_thresholds(self.file.schema_nodes, c) for _, c in specs}
         by_leaf, with_lists = tree.structs_by_leaf(root), tree.list_leaves(root)
-        res, dev, nbytes = decode_spans(self.file, specs, self.dec, self.keep_dict)
+        res, dev, nbytes = self._decode_spans(specs, self.keep_dict)
         self.uploaded_bytes += nbytes
         columns, structs, info = {}, {}, {}
         try:
@@ -1223,7 +1619,7 @@ class FileReader:
         specs = [(rg, c) for c in self.selected]
         if not specs:
             return {}
-        res, dev, nbytes = decode_spans(self.file, specs, self.dec)
+        res, dev, nbytes = self._decode_spans(specs, ())
         self.uploaded_bytes += nbytes
         try:
             return {c: self.dec.download(r, i) for i, ((_, c), r) in enumerate(zip(specs, res))}
